@@ -9,6 +9,11 @@ policy + alpha on even iterations). Env-steps per step = envs x horizon (20).
 
 Run: python bench.py [--gpus N --steps K --warmup W]; for N > 1 under torch.distributed.run
 (one rank per GPU, RCCL). Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value,
+ms_per_step). --dump-outputs DIR also writes what the last timed step left with its caller as
+DIR/<name>.npy. --full adds every other measurement to the line: the phase split, the per-kernel
+durations and roofline, the 4,194,304-env kernel run and the CPU baseline.
 """
 import argparse
 import ctypes
@@ -31,13 +36,21 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=50)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure the phase split, the per-kernel durations and "
+                        "roofline, the 4,194,304-env kernel and the CPU baseline (runs of their own)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the state the last timed step left (networks, observations, newest replay "
+                        "windows) as DIR/<name>.npy")
     p.add_argument("--env", default="QuadTracking")
     p.add_argument("--envs", type=int, default=65536, help="parallel envs per GPU")
     p.add_argument("--policy", choices=["init", "hover"], default="init",
                    help="init: PyTorch default init (SURVEY 8d); hover: action mean [mg,0,0,0], long episodes")
-    p.add_argument("--cpu-seconds", type=float, default=6.0, help="per CPU-baseline leg (1x4 threads, Px1)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-4m", action="store_true", help="skip the 4,194,304-env lockstep-kernel measurement")
+    p.add_argument("--cpu-seconds", type=float, default=6.0,
+                   help="with --full: per CPU-baseline leg (1x4 threads, Px1)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-4m", action="store_true",
+                   help="with --full: skip the 4,194,304-env lockstep-kernel measurement")
     p.add_argument("--no-twin-streams", action="store_true",
                    help="alg_twin_streams off: q1 / q2 branches of the update on one stream (A/B)")
     p.add_argument("--overlap", action="store_true",
@@ -97,6 +110,35 @@ def cpu_baseline(env_name, seconds):
     except (OSError, ValueError, StopIteration, KeyError):
         out["calibration"] = None
     return out
+
+
+DUMP_WINDOWS = 4096  # newest replay windows written by --dump-outputs (about 20 MB at the default config)
+
+
+def dump_outputs(path, rank, world, alg, sampler, buffer):
+    """What a caller of trainer.step() holds after the last timed step, as float32 / float64 .npy:
+    every tensor of the networks' state_dict (net.<key>), the envs' observations (sampler.obs),
+    the replay store's cursor and its newest DUMP_WINDOWS windows, newest first (store.<key>).
+    The seeds are fixed by the arguments, so two runs with the same arguments start alike."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    pre = f"rank{rank}." if world > 1 else ""
+
+    def put(name, t):
+        t = t.detach()
+        t = t.to(torch.float32 if t.dtype in (torch.float16, torch.bfloat16, torch.float32) else torch.float64)
+        np.save(os.path.join(path, pre + name + ".npy"), t.cpu().numpy())
+
+    for k, v in alg.networks.state_dict().items():
+        put("net." + k, v)
+    put("sampler.obs", sampler.obs)
+    cur = buffer.cursor.cpu()
+    put("store.cursor", cur)
+    M, ptr, size = buffer.max_size, int(cur[0]), int(cur[1])
+    rows = (ptr - 1 - torch.arange(min(size, DUMP_WINDOWS), device=buffer.cursor.device)) % M
+    for k, v in buffer.n_step_buf.items():
+        put("store." + k, v[rows])
 
 
 def main():
@@ -166,15 +208,15 @@ def main():
 
     for _ in range(a.warmup):
         one_step()
-    # the horizon emission alone (k_emit_cells via mh_sample_horizon_emit) on the last warm-up
+    # --full: the horizon emission alone (k_emit_cells via mh_sample_horizon_emit) on the last warm-up
     # step's horizon, before the timed region: it rewrites the same store rows (idempotent) and
     # moves no env state, and the window count is then one of the trainer's own steps (after the
     # timed region the init policy's episodes have mostly become short and horizons emit ~1 k)
-    from tools.gputime import time_launches
     trainer.finish_pending()
     emit_diag = None
-    if (hasattr(sampler, "_pack_policy") and getattr(sampler, "_fused_horizon_ok", None)
+    if (a.full and hasattr(sampler, "_pack_policy") and getattr(sampler, "_fused_horizon_ok", None)
             and sampler._fused_horizon_ok(bool(sampler._pack_policy()))):
+        from tools.gputime import time_launches
         h_e, st_e = sampler.envs.handle(), N.stream_of(dev)
         win_dev = torch.zeros(1, dtype=torch.int64, device=dev)
 
@@ -201,6 +243,33 @@ def main():
     value = env_steps_total / elapsed
 
     trainer.finish_pending()
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, rank, world, alg, sampler, buffer)
+    out = {
+        "metric": "env steps/sec (whole node), QuadrotorTracking 65536 envs, 1/2/4/8 MI355X",
+        "value": round(value, 1), "unit": "env_steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": a.full,
+        "config": {"workload": f"{a.env} MSACL NstepOffSerialTrainer.step: {a.envs} envs/GPU x horizon {horizon}, "
+                               f"n-step {sampler.n_step} windows, replay batch 256, full MSACL update",
+                   "env": a.env, "envs_per_gpu": a.envs, "horizon": horizon, "n_step": sampler.n_step,
+                   "replay_batch": 256, "policy": a.policy, "parallelism": f"dp{world}"},
+        "dist_backend": dist_backend, "rccl_ranks": ranks_seen, "dp_rehearsal": dp_rehearsal,
+        "windows_per_step": round(windows_timed / a.steps, 1),
+    }
+
+    def finish(line):
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        elif dp_rehearsal is not None:
+            torch.distributed.destroy_process_group()
+
+    if not a.full:  # the headline alone: everything below takes runs of its own
+        finish(out)
+        return
 
     # ---- phase split (diagnostic, after the timed region): sample() vs replay sample + update,
     # each synchronised, over PH_PAIRS (policy-free, policy) step pairs; per pair the two steps'
@@ -430,30 +499,10 @@ def main():
     if "rollout_step_4m" in kernels:
         roof["frac_4m_envs"] = kernels["rollout_step_4m"]["frac"]
 
-    out = {
-        "metric": "env steps/sec (whole node), QuadrotorTracking 65536 envs, 1/2/4/8 MI355X",
-        "value": round(value, 1), "unit": "env_steps/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(elapsed / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{a.env} MSACL NstepOffSerialTrainer.step: {a.envs} envs/GPU x horizon {horizon}, "
-                               f"n-step {n} windows, replay batch 256, full MSACL update",
-                   "env": a.env, "envs_per_gpu": a.envs, "horizon": horizon, "n_step": n, "replay_batch": 256,
-                   "policy": a.policy, "parallelism": f"dp{world}"},
-        "roofline": roof,
-        "dist_backend": dist_backend, "rccl_ranks": ranks_seen, "dp_rehearsal": dp_rehearsal,
-        "kernels": kernels,
-        "windows_per_step": round(windows_timed / a.steps, 1),
-        "phases": phases,
-    }
+    out.update({"roofline": roof, "kernels": kernels, "phases": phases})
     if rank == 0 and world == 1 and not a.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(a.env, a.cpu_seconds)
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if world > 1:
-        torch.distributed.barrier()
-        torch.distributed.destroy_process_group()
-    elif dp_rehearsal is not None:
-        torch.distributed.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

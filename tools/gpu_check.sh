@@ -21,8 +21,8 @@ for s in $STEPS; do
   case $s in
     tests) run pytest_gpu 900 python -u -m pytest ${TESTS:-tests} -m gpu -q -x --timeout 300 --timeout-method thread -rf -p no:cacheprovider ;;
     smoke) run smoke 600 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 900 python bench.py --steps ${BENCH_STEPS:-20} --warmup ${BENCH_WARMUP:-5} ${BENCH_ARGS:---no-cpu-baseline} ;;
-    hover) run bench_hover 900 python bench.py --steps ${BENCH_STEPS:-20} --warmup ${BENCH_WARMUP:-5} --policy hover --no-cpu-baseline ;;
+    bench) run bench 900 python bench.py --steps ${BENCH_STEPS:-20} --warmup ${BENCH_WARMUP:-5} ${BENCH_ARGS:---full --no-cpu-baseline} ;;
+    hover) run bench_hover 900 python bench.py --steps ${BENCH_STEPS:-20} --warmup ${BENCH_WARMUP:-5} --policy hover --full --no-cpu-baseline ;;
     capture_probe) run capture_probe 300 python -u tools/probes/capture_unjoined_probe.py ;;
     prof) run prof 600 bash tools/profile_bench.sh ;;
     pmc) run pmc 900 bash tools/pmc.sh ;;
