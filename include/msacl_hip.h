@@ -722,6 +722,75 @@ int mh_msacl_policy_combine(const float* loss_q, const float* loss_ppo, const fl
 int mh_msacl_alpha_grad(const float* log_alpha, const float* entropy, float target_entropy, float* grad,
                         void* stream);
 
+/* ---- closed-loop certificate audit (new: the reference only ever evaluates the Lyapunov network
+ * inside the training loss, msacl.py:279-332) ----
+ * The deterministic closed loop (TanhGaussDistribution.mode() actions) is followed from a batch
+ * of initial states WITHOUT autoreset; the caller evaluates V on every observation row, and one
+ * scan checks the bounds alpha1 |x|^2 <= V(x) <= alpha2 |x|^2 and the multi-step decay
+ * V(x_{t+k}) <= (1 - eta)^k V(x_t) along every trajectory.
+ *
+ * Trajectory columns are time-major: q, v [T + 1][E] (q_t = |obs_t|^2 in the cost's summation
+ * order: q[t + 1] * cost_scale is step t's cost bit for bit; v is written by the caller, row t =
+ * V(obs_t)); optional traj_obs [T + 1][E][obs_dim] and traj_act [T][E][act_dim]. Per env: len
+ * (steps taken), status (0 running, 1 terminated, 2 truncated; terminated wins), and the float64
+ * sums ret / cost of the scaled reward / cost (rew_plus_cost.py:18-21 with the struct's scales). */
+typedef struct {
+  float* q;
+  float* v;
+  float* traj_obs; /* nullable */
+  float* traj_act; /* nullable */
+  int32_t* len;
+  int32_t* status;
+  double* ret;
+  double* cost;
+  int64_t num_envs;
+  int32_t T;
+  float reward_scale, cost_scale;
+} mh_audit_traj_t;
+
+/* Per-env results of the scan, each [E] and required. With c / w / s the algorithm's
+ * start_obs_norm_coef / lya_diff_coef / start_lya_coef [n] (as passed to mh_msacl_lyapunov):
+ *   lo_count / hi_count    t in 0..len with V_t < alpha1 q_t / V_t > alpha2 q_t
+ *   lo_excess / hi_excess  max over t of (alpha1 q_t - V_t)+ / (V_t - alpha2 q_t)+
+ *   pairs                  pairs (t, k), k = 1..n, t + k <= len
+ *   lya_viol / lya_worst   pairs with V_{t+k} > s_{k-1} V_t / the largest V_{t+k} - s_{k-1} V_t
+ *                          (-inf without a pair)
+ *   esl_neg                pairs whose exponential-stability label is -1:
+ *                          c_{k-1} sqrt(q_t) - sqrt(q_{t+k}) < 0 (the loss's norm form, >= 0 is +1)
+ *   windows / resid_sum    starts t with t + n <= len / the float64 sum over them of
+ *                          R_t = sum_k w_k max(ESL_{t,k} (V_{t+k+1} - s_k V_t), 0) (float32, k order):
+ *                          lya_diff of msacl.py:324-328 with is_clip_ratio = 1 */
+typedef struct {
+  int32_t* lo_count;
+  int32_t* hi_count;
+  int32_t* pairs;
+  int32_t* lya_viol;
+  int32_t* esl_neg;
+  int32_t* windows;
+  float* lo_excess;
+  float* hi_excess;
+  float* lya_worst;
+  double* resid_sum;
+} mh_certificate_out_t;
+
+/* Start an audit: reset every env to reset_states [E][reset_dim] (or NULL: drawn) with steps = 0,
+ * write obs [E][obs_dim], zero len / status / the sums and q, and write row 0 of q (and traj_obs).
+ * traj->num_envs must equal the handle's. From here until the next mh_env_reset the handle holds
+ * frozen terminal states: reset it before any other stepping call (mh_env_step, mh_rollout_*,
+ * mh_sample_horizon), which would autoreset them. */
+int mh_audit_begin(mh_env_t h, const float* reset_states, float* obs, const mh_audit_traj_t* traj, void* stream);
+/* Lockstep t (0 <= t < T) of the audit for every env still running: action = the clipped mode of
+ * logits [E][2*act_dim], or act_in [E][act_dim] used as given (parity mode); env step; writes obs
+ * (the next policy input), q[t + 1], traj_obs[t + 1], traj_act[t] and the accumulators. An env
+ * that terminated or truncated is frozen: nothing of it is read or written again. */
+int mh_audit_step(mh_env_t h, const float* logits, const float* act_in, float* obs, const mh_audit_traj_t* traj,
+                  int32_t t, void* stream);
+/* The certificate along every trajectory (traj: q, v, len, num_envs, T), 1 <= n <= 64 and
+ * 0 <= T <= max_step, MH_EINVAL otherwise. resid: optional dense [T][E] map of R_t (0 where start
+ * t has no full window). Rows beyond an env's len are never read. */
+int mh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c, const float* w, const float* s,
+                        float alpha1, float alpha2, const mh_certificate_out_t* out, float* resid, void* stream);
+
 /* ---- prioritized replay (new: the reference trainer expects buffer.update_batch(idx, prio),
  * RL/trainer/nstep_off_serial_trainer.py:93-95, but ships no prioritized buffer) ---- */
 /* sum-tree over `capacity` leaves (tree: float64 [2*pow2]); leaf i priority p_i. */

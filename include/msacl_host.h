@@ -42,6 +42,16 @@ int mhh_env_step(mhh_env_t h, const float* act, const float* reset_states, float
 int mhh_env_get_state(mhh_env_t h, float* state, double* xstate, int32_t* steps);
 int mhh_env_set_state(mhh_env_t h, const float* state, const double* xstate, const int32_t* steps);
 
+/* The closed-loop certificate audit, the host twins of mh_audit_begin / mh_audit_step /
+ * mh_certificate_scan (msacl_hip.h: same arguments minus the stream, the same per-env code,
+ * csrc/certificate.h). A handle used for an audit holds frozen terminal states: reset it before
+ * any other stepping call. */
+int mhh_audit_begin(mhh_env_t h, const float* reset_states, float* obs, const mh_audit_traj_t* traj);
+int mhh_audit_step(mhh_env_t h, const float* logits, const float* act_in, float* obs, const mh_audit_traj_t* traj,
+                   int32_t t);
+int mhh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c, const float* w, const float* s,
+                         float alpha1, float alpha2, const mh_certificate_out_t* out, float* resid);
+
 /* MSACL target / certificate math (RL/algorithm/msacl.py), the host twins of mh_msacl_* in
  * msacl_hip.h (same arguments minus the stream): */
 int mhh_msacl_q_target(const float* q1, const float* q2, const float* q1t, const float* q2t, const float* next_logp,

@@ -71,6 +71,28 @@ class WindowStore(ctypes.Structure):
     ]
 
 
+class AuditTraj(ctypes.Structure):
+    """mh_audit_traj_t (include/msacl_hip.h)."""
+    _fields_ = [
+        ("q", c_vp), ("v", c_vp), ("traj_obs", c_vp), ("traj_act", c_vp), ("len", c_vp), ("status", c_vp),
+        ("ret", c_vp), ("cost", c_vp), ("num_envs", c_i64), ("T", c_i32), ("reward_scale", c_f32),
+        ("cost_scale", c_f32),
+    ]
+
+
+class CertificateOut(ctypes.Structure):
+    """mh_certificate_out_t (include/msacl_hip.h)."""
+    _fields_ = [(k, c_vp) for k in ("lo_count", "hi_count", "pairs", "lya_viol", "esl_neg", "windows", "lo_excess",
+                                    "hi_excess", "lya_worst", "resid_sum")]
+
+
+_AUDIT_PROTOS = {  # entry points shared by both libraries (the device ones take a trailing stream)
+    "audit_begin": [c_vp, c_vp, c_vp, ctypes.POINTER(AuditTraj)],
+    "audit_step": [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(AuditTraj), c_i32],
+    "certificate_scan": [ctypes.POINTER(AuditTraj), c_i32, c_vp, c_vp, c_vp, c_f32, c_f32,
+                         ctypes.POINTER(CertificateOut), c_vp],
+}
+
 # name -> (restype, argtypes)
 _PROTOS = {
     "mh_abi_version": (ctypes.c_int, []),
@@ -192,6 +214,7 @@ _PROTOS = {
     "mh_per_set_new": (ctypes.c_int, [c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     "mh_per_sample": (ctypes.c_int, [c_vp, c_i64, c_vp, c_u64, c_u64, c_i64, c_f32, c_vp, c_vp, c_vp]),
 }
+_PROTOS.update({"mh_" + k: (ctypes.c_int, v + [c_vp]) for k, v in _AUDIT_PROTOS.items()})
 
 _lib = None
 
@@ -254,6 +277,7 @@ _HOST_PROTOS = {
     "mhh_msacl_ratio0": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp]),
     "mhh_msacl_ratio0_backward": (ctypes.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp]),
 }
+_HOST_PROTOS.update({"mhh_" + k: (ctypes.c_int, v) for k, v in _AUDIT_PROTOS.items()})
 _host = None
 
 

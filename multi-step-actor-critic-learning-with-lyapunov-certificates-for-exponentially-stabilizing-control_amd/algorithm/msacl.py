@@ -308,6 +308,15 @@ class _Scratch:
         self.dq_obj, self.dlogp_obj, self.dlp_obj = f(2, B, n), f(B, n), f(B, n)
 
 
+def certificate_coefs(n, lya_eta, retrace_lambda, alpha1, alpha2):
+    """The certificate's coefficient vectors [n] (msacl.py:153-164, same torch expressions, CPU
+    float32): start_obs_norm_coef, lya_diff_coef, start_lya_coef. The Lyapunov loss and the
+    closed-loop audit (trainer/certificate_auditor.py) both use them."""
+    c = (torch.tensor(1 - lya_eta) ** torch.arange(1, n + 1) * torch.tensor(alpha2 / alpha1)) ** 0.5
+    w = torch.pow(retrace_lambda, torch.arange(n))
+    return c, w / torch.sum(w), torch.pow((1 - lya_eta), torch.arange(n) + 1)
+
+
 class MSACL:
     def __init__(self, gamma: float = 0.99, retrace_lambda: float = 0.95, lya_eta: float = 0.15,
                  tau: float = 0.005, alpha: float = math.e, auto_alpha: bool = True,
@@ -346,13 +355,9 @@ class MSACL:
         self.alpha1 = kwargs.get("alpha1", 1.0)
         self.alpha2 = kwargs.get("alpha2", 2.0)
         self.clip_coef = kwargs.get("clip_coef", 0.1)
-        n = self.n_step
-        # coefficient vectors (msacl.py:153-164), same torch expressions, on this device
-        self.start_obs_norm_coef = ((torch.tensor(1 - self.lya_eta) ** torch.arange(1, n + 1)
-                                     * torch.tensor(self.alpha2 / self.alpha1)) ** 0.5).to(self.device).contiguous()
-        w = torch.pow(self.retrace_lambda, torch.arange(n))
-        self.lya_diff_coef = (w / torch.sum(w)).to(self.device).contiguous()
-        self.start_lya_coef = torch.pow((1 - self.lya_eta), torch.arange(n) + 1).to(self.device).contiguous()
+        self.start_obs_norm_coef, self.lya_diff_coef, self.start_lya_coef = (
+            t.to(self.device).contiguous() for t in certificate_coefs(
+                self.n_step, self.lya_eta, self.retrace_lambda, self.alpha1, self.alpha2))
         self._scratch = {}
         self.last_priority = None
         self._neg_one = torch.tensor(-1.0, device=self.device)

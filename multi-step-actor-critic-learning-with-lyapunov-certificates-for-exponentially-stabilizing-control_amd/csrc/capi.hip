@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "msacl_hip.h"
+#include "certificate.h"
 #include "rollout.h"
 #include "sample_fused.h"
 
@@ -592,6 +593,99 @@ int mh_env_set_state(mh_env_t h, const float* state, const double* xstate, const
   if (xstate && h->info.xstate_dim > 0)
     MH_HIP(mh::launch_transpose_f64(xstate, h->xstate, h->info.xstate_dim, h->E, false, st));
   if (steps) MH_HIP(hipMemcpyAsync(h->steps, steps, sizeof(int32_t) * h->E, hipMemcpyDeviceToDevice, st));
+  return MH_OK;
+}
+
+// ------------------------------------------------------------------ certificate audit
+static int audit_args(mh_env_t h, const mh_audit_traj_t* tr, const char* who, mh::AuditArgs* a) {
+  if (!h || !tr) return fail(MH_EINVAL, std::string(who) + ": null handle or trajectory");
+  if (tr->num_envs != h->E) return fail(MH_EINVAL, std::string(who) + ": trajectory num_envs differs from the handle's");
+  if (tr->T < 0 || tr->T > h->info.max_step) return fail(MH_EINVAL, std::string(who) + ": T out of range");
+  if (!tr->q || !tr->len || !tr->status || !tr->ret || !tr->cost)
+    return fail(MH_EINVAL, std::string(who) + ": incomplete trajectory (q, len, status, ret, cost)");
+  std::memset(a, 0, sizeof(*a));
+  a->E = h->E;
+  a->state = h->state;
+  a->xstate = h->xstate;
+  a->steps = h->steps;
+  a->tab = h->tab;
+  a->len = tr->len;
+  a->status = tr->status;
+  a->ret = tr->ret;
+  a->cost = tr->cost;
+  a->reward_scale = tr->reward_scale;
+  a->cost_scale = tr->cost_scale;
+  return MH_OK;
+}
+
+int mh_audit_begin(mh_env_t h, const float* reset_states, float* obs, const mh_audit_traj_t* traj, void* stream) {
+  mh::AuditArgs a;
+  if (int rc = audit_args(h, traj, "mh_audit_begin", &a)) return rc;
+  if (!obs) return fail(MH_EINVAL, "mh_audit_begin: null obs");
+  if (int rc = mh_env_reset(h, reset_states, obs, stream)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  MH_HIP(hipMemsetAsync(traj->q, 0, sizeof(float) * ((size_t)traj->T + 1) * h->E, st));
+  a.obs = obs;
+  a.q_row = traj->q;
+  a.traj_obs = traj->traj_obs;
+  MH_HIP(mh::launch_audit_begin(h->env_id, a, st));
+  return MH_OK;
+}
+
+int mh_audit_step(mh_env_t h, const float* logits, const float* act_in, float* obs, const mh_audit_traj_t* traj,
+                  int32_t t, void* stream) {
+  mh::AuditArgs a;
+  if (int rc = audit_args(h, traj, "mh_audit_step", &a)) return rc;
+  if (!obs) return fail(MH_EINVAL, "mh_audit_step: null obs");
+  if (!logits && !act_in) return fail(MH_EINVAL, "mh_audit_step: need logits or act_in");
+  if (t < 0 || t >= traj->T) return fail(MH_EINVAL, "mh_audit_step: t outside [0, T)");
+  if (int rc = flush_pending(h, stream)) return rc;
+  const int64_t E = h->E;
+  a.obs = obs;
+  a.logits = act_in ? nullptr : logits;
+  a.act_in = act_in;
+  a.q_row = traj->q + ((int64_t)t + 1) * E;
+  a.traj_obs = traj->traj_obs ? traj->traj_obs + ((int64_t)t + 1) * E * h->info.obs_dim : nullptr;
+  a.traj_act = traj->traj_act ? traj->traj_act + (int64_t)t * E * h->info.act_dim : nullptr;
+  MH_HIP(mh::launch_audit_step(h->env_id, a, (hipStream_t)stream));
+  return MH_OK;
+}
+
+int mh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c, const float* w, const float* s,
+                        float alpha1, float alpha2, const mh_certificate_out_t* out, float* resid, void* stream) {
+  if (!traj || !out || !c || !w || !s) return fail(MH_EINVAL, "mh_certificate_scan: null argument");
+  if (n < 1 || n > mh::CERT_MAX_N) return fail(MH_EINVAL, "mh_certificate_scan: n outside [1, 64]");
+  if (traj->T < 0 || traj->T > mh::MAX_STEP) return fail(MH_EINVAL, "mh_certificate_scan: T outside [0, max_step]");
+  if (traj->num_envs <= 0 || !traj->q || !traj->v || !traj->len)
+    return fail(MH_EINVAL, "mh_certificate_scan: incomplete trajectory (q, v, len)");
+  if (!out->lo_count || !out->hi_count || !out->pairs || !out->lya_viol || !out->esl_neg || !out->windows ||
+      !out->lo_excess || !out->hi_excess || !out->lya_worst || !out->resid_sum)
+    return fail(MH_EINVAL, "mh_certificate_scan: incomplete outputs");
+  mh::ScanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.E = traj->num_envs;
+  a.v = traj->v;
+  a.q = traj->q;
+  a.len = traj->len;
+  a.T = traj->T;
+  a.n = n;
+  a.c = c;
+  a.w = w;
+  a.s = s;
+  a.alpha1 = alpha1;
+  a.alpha2 = alpha2;
+  a.lo_count = out->lo_count;
+  a.hi_count = out->hi_count;
+  a.pairs = out->pairs;
+  a.lya_viol = out->lya_viol;
+  a.esl_neg = out->esl_neg;
+  a.windows = out->windows;
+  a.lo_excess = out->lo_excess;
+  a.hi_excess = out->hi_excess;
+  a.lya_worst = out->lya_worst;
+  a.resid_sum = out->resid_sum;
+  a.resid = resid;
+  MH_HIP(mh::launch_certificate_scan(a, (hipStream_t)stream));
   return MH_OK;
 }
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "msacl_host.h"
+#include "certificate.h"
 #include "reset_draw.h"
 
 #pragma clang fp contract(off)
@@ -108,6 +109,55 @@ void step_all(HostEnv& h, const float* act, const float* rs_in, float* next_obs,
     if (reward) reward[e] = r;
     if (term_out) term_out[e] = term ? 1 : 0;
     if (trunc_out) trunc_out[e] = trunc ? 1 : 0;
+  }
+}
+
+// mh_audit_begin / mh_audit_step over the batch (certificate.h: the kernels' per-env code)
+template <class Env>
+void audit_begin_all(HostEnv& h, const float* rs_in, float* obs, const mh_audit_traj_t* tr) {
+  constexpr int D = Env::D;
+  const int64_t E = h.E;
+  for (int64_t i = 0; i < ((int64_t)tr->T + 1) * E; ++i) tr->q[i] = 0.0f;
+  for (int64_t e = 0; e < E; ++e) {
+    reset_one<Env>(h, e, rs_in ? rs_in + e * Env::RS : nullptr, obs + e * D);
+    tr->q[e] = mh::audit_q<D>(obs + e * D);
+    if (tr->traj_obs)
+      for (int i = 0; i < D; ++i) tr->traj_obs[e * D + i] = obs[e * D + i];
+    tr->len[e] = 0;
+    tr->status[e] = mh::AUDIT_RUNNING;
+    tr->ret[e] = 0.0;
+    tr->cost[e] = 0.0;
+  }
+}
+
+template <class Env>
+void audit_step_all(HostEnv& h, const float* logits, const float* act_in, float* obs, const mh_audit_traj_t* tr,
+                    int t) {
+  constexpr int D = Env::D, A = Env::A, S = Env::S, XS = Env::XS;
+  const int64_t E = h.E;
+  const double* tab = h.tab.empty() ? nullptr : h.tab.data();
+  for (int64_t e = 0; e < E; ++e) {
+    if (tr->status[e] != mh::AUDIT_RUNNING) continue;  // frozen
+    float u[A];
+    if (act_in) {
+      for (int i = 0; i < A; ++i) u[i] = act_in[e * A + i];
+    } else {
+      mh::audit_mode_action<Env>(logits + e * 2 * A, u);
+    }
+    float obs2[D], q, r;
+    const int k = h.steps[e];
+    const int status = mh::audit_env_step<Env>(&h.state[e * S], &h.xstate[e * (XS > 0 ? XS : 1)], k, u, tab, obs2, &q, &r);
+    h.steps[e] = k + 1;
+    for (int i = 0; i < D; ++i) obs[e * D + i] = obs2[i];
+    tr->q[((int64_t)t + 1) * E + e] = q;
+    if (tr->traj_obs)
+      for (int i = 0; i < D; ++i) tr->traj_obs[(((int64_t)t + 1) * E + e) * D + i] = obs2[i];
+    if (tr->traj_act)
+      for (int i = 0; i < A; ++i) tr->traj_act[((int64_t)t * E + e) * A + i] = u[i];
+    tr->len[e] += 1;
+    tr->status[e] = status;
+    tr->ret[e] += (double)(r * tr->reward_scale);
+    tr->cost[e] += (double)(q * tr->cost_scale);
   }
 }
 
@@ -231,6 +281,63 @@ int mhh_env_set_state(mhh_env_t hv, const float* state, const double* xstate, co
   if (state) memcpy(h->state.data(), state, sizeof(float) * h->state.size());
   if (xstate && h->XS > 0) memcpy(h->xstate.data(), xstate, sizeof(double) * (size_t)h->E * h->XS);
   if (steps) memcpy(h->steps.data(), steps, sizeof(int32_t) * h->steps.size());
+  return MH_OK;
+}
+
+// ------------------------------------------------------------------ certificate audit (host)
+static int audit_check(HostEnv* h, const mh_audit_traj_t* tr, const char* who) {
+  if (!h || !tr) return fail(MH_EINVAL, std::string(who) + ": null handle or trajectory");
+  if (tr->num_envs != h->E) return fail(MH_EINVAL, std::string(who) + ": trajectory num_envs differs from the handle's");
+  if (tr->T < 0 || tr->T > mh::MAX_STEP) return fail(MH_EINVAL, std::string(who) + ": T out of range");
+  if (!tr->q || !tr->len || !tr->status || !tr->ret || !tr->cost)
+    return fail(MH_EINVAL, std::string(who) + ": incomplete trajectory (q, len, status, ret, cost)");
+  return MH_OK;
+}
+
+int mhh_audit_begin(mhh_env_t hv, const float* reset_states, float* obs, const mh_audit_traj_t* traj) {
+  HostEnv* h = static_cast<HostEnv*>(hv);
+  if (int rc = audit_check(h, traj, "mhh_audit_begin")) return rc;
+  if (!obs) return fail(MH_EINVAL, "mhh_audit_begin: null obs");
+  MHH_DISPATCH(h->env_id, audit_begin_all<Env>(*h, reset_states, obs, traj));
+  return MH_OK;
+}
+
+int mhh_audit_step(mhh_env_t hv, const float* logits, const float* act_in, float* obs, const mh_audit_traj_t* traj,
+                   int32_t t) {
+  HostEnv* h = static_cast<HostEnv*>(hv);
+  if (int rc = audit_check(h, traj, "mhh_audit_step")) return rc;
+  if (!obs) return fail(MH_EINVAL, "mhh_audit_step: null obs");
+  if (!logits && !act_in) return fail(MH_EINVAL, "mhh_audit_step: need logits or act_in");
+  if (t < 0 || t >= traj->T) return fail(MH_EINVAL, "mhh_audit_step: t outside [0, T)");
+  MHH_DISPATCH(h->env_id, audit_step_all<Env>(*h, logits, act_in, obs, traj, t));
+  return MH_OK;
+}
+
+int mhh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c, const float* w, const float* s,
+                         float alpha1, float alpha2, const mh_certificate_out_t* out, float* resid) {
+  if (!traj || !out || !c || !w || !s) return fail(MH_EINVAL, "mhh_certificate_scan: null argument");
+  if (n < 1 || n > mh::CERT_MAX_N) return fail(MH_EINVAL, "mhh_certificate_scan: n outside [1, 64]");
+  if (traj->T < 0 || traj->T > mh::MAX_STEP) return fail(MH_EINVAL, "mhh_certificate_scan: T outside [0, max_step]");
+  if (traj->num_envs <= 0 || !traj->q || !traj->v || !traj->len)
+    return fail(MH_EINVAL, "mhh_certificate_scan: incomplete trajectory (q, v, len)");
+  if (!out->lo_count || !out->hi_count || !out->pairs || !out->lya_viol || !out->esl_neg || !out->windows ||
+      !out->lo_excess || !out->hi_excess || !out->lya_worst || !out->resid_sum)
+    return fail(MH_EINVAL, "mhh_certificate_scan: incomplete outputs");
+  for (int64_t e = 0; e < traj->num_envs; ++e) {
+    mh::CertRow o;
+    mh::certificate_scan_env(traj->v, traj->q, traj->num_envs, e, traj->len[e], traj->T, n, c, w, s, alpha1, alpha2,
+                             resid, &o);
+    out->lo_count[e] = o.lo_count;
+    out->hi_count[e] = o.hi_count;
+    out->pairs[e] = o.pairs;
+    out->lya_viol[e] = o.lya_viol;
+    out->esl_neg[e] = o.esl_neg;
+    out->windows[e] = o.windows;
+    out->lo_excess[e] = o.lo_excess;
+    out->hi_excess[e] = o.hi_excess;
+    out->lya_worst[e] = o.lya_worst;
+    out->resid_sum[e] = o.resid_sum;
+  }
   return MH_OK;
 }
 

@@ -144,6 +144,42 @@ struct GatherPlan {
   int nseg;
 };
 
+// the certificate audit (certificate.hip): one lockstep of the deterministic closed loop without
+// autoreset, and the scan of the finished V / q trajectories
+struct AuditArgs {
+  int64_t E;
+  float* state;       // [S][E]
+  double* xstate;     // [XS][E]
+  int32_t* steps;     // [E]
+  const double* tab;
+  float* obs;         // [E][D] out: next policy input of every live env
+  const float* logits;  // [E][2A] (mode action) or null
+  const float* act_in;  // [E][A] injected actions, used as given, or null
+  float* q_row;       // row t + 1 of q [T + 1][E]
+  float* traj_obs;    // row t + 1 of [T + 1][E][D] or null
+  float* traj_act;    // row t of [T][E][A] or null
+  int32_t* len;       // [E]
+  int32_t* status;    // [E]
+  double* ret;        // [E]
+  double* cost;       // [E]
+  float reward_scale, cost_scale;
+};
+struct ScanArgs {
+  int64_t E;
+  const float *v, *q;  // [T + 1][E]
+  const int32_t* len;  // [E]
+  int T, n;
+  const float *c, *w, *s;  // [n]
+  float alpha1, alpha2;
+  int32_t *lo_count, *hi_count, *pairs, *lya_viol, *esl_neg, *windows;
+  float *lo_excess, *hi_excess, *lya_worst;
+  double* resid_sum;
+  float* resid;  // [T][E] or null
+};
+hipError_t launch_audit_begin(int env_id, const AuditArgs& a, hipStream_t st);  // a.obs: the reset's observations
+hipError_t launch_audit_step(int env_id, const AuditArgs& a, hipStream_t st);
+hipError_t launch_certificate_scan(const ScanArgs& a, hipStream_t st);
+
 hipError_t launch_rollout(int env_id, const StepArgs& a, hipStream_t st);
 hipError_t launch_gae(const float* val, const float* val2, const float* rew, const uint8_t* done, int64_t E,
                       int H, double gamma, double lam, float* adv, float* ret, hipStream_t st);

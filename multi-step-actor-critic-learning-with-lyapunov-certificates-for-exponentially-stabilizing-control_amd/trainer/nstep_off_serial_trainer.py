@@ -8,6 +8,9 @@ model_update -> log / save / evaluate. Differences, all at the device boundary:
   * the HIP sampler is bound to the device buffer at construction so windows are emitted in
     place;
   * tensorboard is optional (in-memory writer when absent);
+  * `certificate_interval` = K > 0 (default 0: off, nothing is built or run) audits the learned
+    certificate in closed loop every K iterations (trainer/certificate_auditor.py) and logs
+    Certificate/bounds_ok, Certificate/decay_ok and Certificate/residual;
   * overlapped sampling (`trainer_overlap_sampling`, off by default): when the
     update of iteration k leaves the policy unchanged (k % policy_frequency != 0), the sampling of
     iteration k + 1 only depends on what precedes that update, so it is enqueued on a second stream
@@ -84,6 +87,11 @@ class NstepOffSerialTrainer:
         self.graph_step = bool(kwargs.get("trainer_graph_step", os.environ.get("MSACL_GRAPH_STEP", "1") != "0"))
         self._step_graphs = {}
         self._packed_state = None  # (sampler key, policy updates, policy version) at the last graphed pack
+        # closed-loop certificate audit every certificate_interval iterations (0: never; the
+        # auditor is only built when it is on)
+        self.certificate_interval = int(kwargs.get("certificate_interval", 0))
+        self.auditor = None
+        self._auditor_kwargs = kwargs if self.certificate_interval > 0 else None
         self.start_time = time.time()
 
     def _sample(self):
@@ -238,6 +246,20 @@ class NstepOffSerialTrainer:
             self.save_apprfunc()
         if self.evaluator is not None and self.iteration % self.eval_interval == 0 and self.iteration > 0:
             self._evaluate()
+        if self.certificate_interval > 0 and self.iteration % self.certificate_interval == 0 and self.iteration > 0:
+            self._audit_certificate()
+
+    def _audit_certificate(self):
+        """Audit num_audit_states drawn initial states with the current networks (eager, outside
+        every graph) and log the summary."""
+        if self.auditor is None:
+            from ..create_pkg.create_auditor import create_auditor
+            kw = dict(self._auditor_kwargs, device=self.sample_device)
+            self.auditor = create_auditor(kw.pop("auditor_name", "certificate_auditor"), networks=self.networks, **kw)
+        summary = self.auditor.audit()["summary"]
+        if self.is_main:
+            for k in ("bounds_ok", "decay_ok", "residual"):
+                self.writer.add_scalar(tb_tags["certificate_" + k], summary[k], self.iteration)
 
     def _evaluate(self):
         with ModuleOnDevice(self.networks, getattr(self.evaluator, "device", self.sample_device)):
@@ -278,7 +300,7 @@ class NstepOffSerialTrainer:
         if fin is not None:
             fin()
         self._step_graphs = {}  # (their captured work references the parts' device buffers)
-        for part in (self.sampler, self.alg, self.evaluator):
+        for part in (self.sampler, self.alg, self.evaluator, self.auditor):
             close = getattr(part, "close", None)
             if close is not None:
                 close()

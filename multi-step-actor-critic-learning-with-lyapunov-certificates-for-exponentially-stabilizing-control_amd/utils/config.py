@@ -23,6 +23,7 @@ def default_msacl_args(**overrides):
         buffer_name="nstep_replay_buffer", buffer_warm_size=int(5e3), buffer_max_size=int(1e6), replay_batch_size=256,
         eval_env_seed=2, is_parallel_eval=True, evaluator_name="evaluator", num_eval_episode=5, eval_interval=1000,
         eval_save=False, save_folder=None, apprfunc_save_interval=50000, log_save_interval=50000,
+        auditor_name="certificate_auditor", num_audit_states=1024, audit_horizon=1000,
     )
     a.update(overrides)
     return a

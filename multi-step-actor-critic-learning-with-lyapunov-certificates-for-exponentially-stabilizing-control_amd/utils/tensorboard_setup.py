@@ -20,6 +20,9 @@ tb_tags = {
     "alg_time": "Time/Algorithm time [ms]-RL iter",
     "sampler_time": "Time/Sampler time [ms]-RL iter",
     "env_steps_per_sec": "Time/Env steps per second-RL iter",
+    "certificate_bounds_ok": "Certificate/bounds_ok",
+    "certificate_decay_ok": "Certificate/decay_ok",
+    "certificate_residual": "Certificate/residual",
 }
 
 
