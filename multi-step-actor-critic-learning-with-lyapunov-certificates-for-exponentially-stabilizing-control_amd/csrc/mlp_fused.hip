@@ -172,9 +172,10 @@ __device__ __forceinline__ void layer_cols(const float* in, __amdgpu_buffer_rsrc
 //      2^e (from the tile's max |value|: every scaled value <= 2^14), then split;
 //   B: eight consecutive floats of weight row n (W [N][K] row-major: two global float4 loads per
 //      16-column block and 32-deep K-step), times the fixed WX = 2^10, then split: the f16 lo of a
-//      weight in [2^-13, 64) is a normal number, so hi + lo keeps 22 bits of it; a weight of 64 or
-//      more overflows its f16 hi, the tile's accumulators come out non-finite, and that row tile
-//      is recomputed by the f32 layer (x3_redo_nonfinite: cold, the bits of the f32 path);
+//      weight in [2^-13, 64) is a normal number, so hi + lo keeps 22 bits of it (a smaller one keeps
+//      its f16 subnormals: an absolute 2^-35); a weight of 63.984375 or more overflows its f16 hi, the
+//      tile's accumulators come out non-finite, and that row tile is recomputed in plain
+//      arithmetic (x3_redo_nonfinite: cold);
 // the accumulators carry 2^e WX, undone exactly (powers of two) before the bias and activation.
 // A value is split in one rounding each way: hi = f16(v k), lo = f16(v k - hi) (v_fma_mix, the
 // product and difference exact inside the fused multiply-add).
@@ -264,7 +265,9 @@ __device__ __forceinline__ void layer_cols_run_x3(const float* in, const float (
 }
 
 // the largest |value| of each row tile of an epilogue's output, over the workgroup (LDS atomic max
-// on the bits: non-negative floats order as their bit patterns; NaN stays the max)
+// on the bits: non-negative floats order as their bit patterns). fmaxf drops a NaN, here and in the
+// epilogue's running max, so a NaN never reaches the scale: a tile holding one is scaled by its
+// finite values and caught by x3_redo_nonfinite alone, through its non-finite accumulators
 template <int RT>
 __device__ __forceinline__ void tile_max_publish(const float (&m)[RT], uint32_t* smax) {
 #pragma unroll
@@ -289,18 +292,37 @@ __device__ __forceinline__ void tile_scales(const uint32_t* smax, float (&sc)[RT
 }
 
 // The row tiles whose split-f16 accumulators came out non-finite (a weight of 64 or more, or a
-// non-finite input, which the f32 layer turns into the same non-finite values) are recomputed by
-// the f32 layer, 2^e WX-scaled so the epilogue's unscale applies unchanged. Wave-uniform and cold.
+// non-finite input) are recomputed in plain arithmetic, 2^e WX-scaled so the epilogue's unscale
+// applies unchanged. Wave-uniform and cold, so precision comes first: the products of two floats are
+// exact in double and the 256-term sum is rounded to f32 once, which keeps such a tile inside the
+// split layers' error bound (the f32 MFMA chain rounds 64 times at the size of the running sum: with
+// one dominant weight, which is what brings a tile here, that was 1.3 x the split bound). A
+// non-finite input still gives non-finite values: NaN and Inf pass through double.
+// The MFMA's C map: column n0 + 16 j + (lane & 15), rows 4 (lane >> 4) + q.
 struct Acc4 {
   f32x4 v[4];
 };
 template <int SIN>
 __device__ __noinline__ Acc4 x3_redo_tile(const float* in, __amdgpu_buffer_rsrc_t wr, int n0, int lane, float s) {
-  f32x4 a1[1][4] = {};
-  layer_cols<SIN, HID / 16, 1>(in, wr, n0, lane, a1);
+  const int c = lane & 15, g = lane >> 4;
   Acc4 r;
+#pragma unroll  // (r.v[j] stays in registers)
+  for (int j = 0; j < 4; ++j) {
+    const int n = n0 + 16 * j + c;
+    double sum[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll 1
+    for (int k = 0; k < HID; k += 4) {
+      const f32x4 w = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wr, (n * HID + k) * 4, 0, 0));
 #pragma unroll
-  for (int j = 0; j < 4; ++j) r.v[j] = mul4_scalar(a1[0][j], s);
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 av = *reinterpret_cast<const f32x4*>(in + (4 * g + q) * SIN + k);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) sum[q] += (double)av[t] * (double)w[t];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) r.v[j][q] = (float)sum[q] * s;
+  }
   return r;
 }
 template <int SIN, int RT>

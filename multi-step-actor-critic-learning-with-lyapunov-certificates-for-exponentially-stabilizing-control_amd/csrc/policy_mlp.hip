@@ -469,7 +469,11 @@ __global__ __launch_bounds__(256, 1) void k_policy_forward_x6(const float* __res
 // scaling, exact in f32: each layer's weights by sw_l (pack time, max |W_l| * sw_l <= 2^14) and
 // each env's input column of each layer by a per-env power of two from a bound on its magnitude
 // (obs: max |obs|; H1: R1 max(1, max |obs|); H2: R2 max(1, bound(H1))), so every split operand is
-// <= 2^14 whatever the observation; accumulators are unscaled exactly (power-of-two products) and
+// <= 2^14 while the largest of those bounds is below 2^54 (pm_scale_exp's clamp; |obs| up to about
+// 1e14 for weights of the usual size: tests/test_gpu_policy_mlp.py holds 1e12 to the bound). An env
+// past that range, or with a NaN or infinite observation, gets NaN logits (policy_x3.h
+// pm_out_of_range) and leaves every other env's bits alone. Accumulators are unscaled exactly
+// (power-of-two products) and
 // the biases join after the unscaling (b1 rides in the MFMA as the weight of a constant input).
 // The splits' subnormal floor is 2^-25 in scaled units, i.e. <= 2^-39 of the operand bound.
 // Layer 2 as k_policy_forward_x6 (LDS-staged W2 chunks, NT = 2 tiles per wave, double-buffered,
@@ -671,10 +675,22 @@ void k_policy_forward_x3(const float* __restrict__ P,
     for (int j = 0; j < 8; ++j) {
       const int k = 8 * (lane >> 5) + j;
       x[j] = k < D ? obs[brow * D + k] : (k == D ? 1.0f : 0.0f);
-      m = fmaxf(m, fabsf(x[j]));
+      m = pm_absmax(m, x[j]);  // keeps a NaN
     }
-    m = fmaxf(m, __shfl_xor(m, 32));  // lanes l and l ^ 32 hold the same env
+    m = pm_absmax(m, __shfl_xor(m, 32));  // lanes l and l ^ 32 hold the same env
+    // an env outside the split's range (policy_x3.h pm_out_of_range) runs on zeros, marked for the
+    // store by an ex[0] no env in range has (a wave-uniform branch: no wave takes it in a healthy run)
+    const bool out = pm_out_of_range(m, R1, R2);  // (m: the same on both lanes of the env)
     ex[0] = pm_scale_exp(m);
+    if (__builtin_expect(__any(out), 0)) {
+      if (out) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (8 * (lane >> 5) + j < D) x[j] = 0.0f;
+        m = 1.0f;
+        ex[0] = PM_EX0_OUT_OF_RANGE;
+      }
+    }
     const float b1v = R1 * m;
     ex[1] = pm_scale_exp(b1v);
     ex[2] = pm_scale_exp(R2 * fmaxf(1.0f, b1v));
@@ -894,11 +910,12 @@ void k_policy_forward_x3(const float* __restrict__ P,
     phase(B0{}, PM_NB - 2, false);
     phase(B1{}, PM_NB - 1, true);
     // logits: registers 0..3 of acc[t][0] hold outputs 4 ((lane >> 4) & 1) + i of env column
-    // pm_l3_env(lane), in units of sw3 * 2^ex[2] of that env (its exponents live on that env's lane)
+    // pm_l3_env(lane), in units of sw3 * 2^ex[2] of that env (its exponents live on that env's lane);
+    // an out-of-range env's unit is NaN: every logit of its row is NaN
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int e = pm_l3_env(lane);
-      const float iu = __shfl(isw3 * pm_pow2(-ex[t][2]), e);
+      const float iu = __shfl(ex[t][0] == PM_EX0_OUT_OF_RANGE ? __builtin_nanf("") : isw3 * pm_pow2(-ex[t][2]), e);
       const int o0 = 4 * ((lane >> 4) & 1);
       const int64_t b = (t0 + t) * 32 + e;
       if (t0 + t < ntiles && b < E && o0 < N3) {

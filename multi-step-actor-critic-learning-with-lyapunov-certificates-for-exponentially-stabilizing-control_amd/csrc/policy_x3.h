@@ -73,6 +73,30 @@ __device__ __forceinline__ int pm_scale_exp(float bound) {  // 14 - ceil(log2(bo
   return k < -40 ? -40 : (k > 40 ? 40 : k);
 }
 
+// The observation range of the split. pm_scale_exp clamps at k = -40, i.e. a bound of 2^54 or more
+// no longer scales below 2^14, and a NaN passes fmaxf unseen while relu_raw (v_max_f32) turns a
+// quiet NaN into 0: such an env would get finite logits computed from garbage, and a +Inf in its
+// H2 would reach its layer-3 partner env (pm_l3_row_half: 0 * Inf = NaN). So an env with a NaN
+// among its observations, or with one of its bounds (m = max(1, max |obs|), R1 m, R2 max(1, R1 m);
+// an infinite observation makes m infinite) not below 2^54, is out of range: the kernels feed
+// zeros for it (every operand finite, its tile mates untouched) and multiply its logits by NaN at
+// the store. With the usual R1, R2 of a few units that is |obs| up to about 1e14.
+// The mark needs no variable of its own: m >= 1 gives every env in range an observation exponent
+// ex[0] = pm_scale_exp(m) <= 13, so an out-of-range env carries ex[0] = 14 (its zeros stay zeros and
+// its constant-1 bias input becomes 2^14, still an exact f16), and the store reads the mark there.
+constexpr float PM_BOUND_LIMIT = 18014398509481984.0f;  // 2^54
+constexpr int PM_EX0_OUT_OF_RANGE = 14;
+// The running max of |x| on the bit patterns: non-negative floats order as their bits, with Inf above
+// every finite value and a NaN above Inf, so unlike fmaxf it keeps a NaN (for finite values: fmaxf's bits).
+__device__ __forceinline__ float pm_absmax(float m, float x) {
+  const uint32_t a = __float_as_uint(m), b = __float_as_uint(x) & 0x7fffffffu;
+  return __uint_as_float(a > b ? a : b);
+}
+__device__ __forceinline__ bool pm_out_of_range(float m, float R1, float R2) {  // m from pm_absmax
+  const float b1v = R1 * m;
+  return !(m < PM_BOUND_LIMIT && b1v < PM_BOUND_LIMIT && R2 * fmaxf(1.0f, b1v) < PM_BOUND_LIMIT);
+}
+
 // sw1..3, their inverses, and R1, R2 rounded up (the f32 sums above are upper bounds only up to
 // their own rounding) from the raw magnitudes
 struct PmScales {

@@ -282,10 +282,22 @@ __device__ void policy_pass(const FusedArgs& a, const PolicyLds& L, int pw, int 
     for (int j = 0; j < 8; ++j) {
       const int k = 8 * (lane >> 5) + j;
       x[j] = k < DD ? L.obs[row * DD + k] : (k == DD ? 1.0f : 0.0f);
-      m = fmaxf(m, fabsf(x[j]));
+      m = pm_absmax(m, x[j]);  // keeps a NaN
     }
-    m = fmaxf(m, __shfl_xor(m, 32));
+    m = pm_absmax(m, __shfl_xor(m, 32));
+    // an env outside the split's range (policy_x3.h pm_out_of_range) runs on zeros, marked for the
+    // store by an ex[0] no env in range has (a wave-uniform branch: no wave takes it in a healthy run)
+    const bool out = pm_out_of_range(m, R1, R2);  // (m: the same on both lanes of the env)
     ex[0] = pm_scale_exp(m);
+    if (__builtin_expect(__any(out), 0)) {
+      if (out) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (8 * (lane >> 5) + j < DD) x[j] = 0.0f;
+        m = 1.0f;
+        ex[0] = PM_EX0_OUT_OF_RANGE;
+      }
+    }
     const float b1v = R1 * m;
     ex[1] = pm_scale_exp(b1v);
     ex[2] = pm_scale_exp(R2 * fmaxf(1.0f, b1v));
@@ -493,10 +505,10 @@ __device__ void policy_pass(const FusedArgs& a, const PolicyLds& L, int pw, int 
   }
   // logits rows, the same expression as k_policy_forward_x3's store: lane l stores outputs
   // 4 ((l >> 4) & 1) + i of env pm_l3_env(l) — one 16-byte (N3 = 8, 4) or 4-byte (N3 = 2, 6) store
-  // per lane — with that env's unit 2^-ex[2] / sw3 from the env's own lane
+  // per lane — with that env's unit 2^-ex[2] / sw3 from the env's own lane (NaN for an out-of-range env)
   MH_STAMP(a, pass_no, 19);
   const int erow = pm_l3_env(lane);
-  const float iu = __shfl(isw3 * pm_pow2(-ex[2]), erow);
+  const float iu = __shfl(ex[0] == PM_EX0_OUT_OF_RANGE ? __builtin_nanf("") : isw3 * pm_pow2(-ex[2]), erow);
   const int row = row0 + erow;
   const int o0 = 4 * ((lane >> 4) & 1);
   float v[4];

@@ -143,6 +143,41 @@ def test_emission_relaunch_rewrites_the_same_rows(tmp_path):
     assert N.lib().mh_sample_horizon_emit(a._h, a.horizon, ctypes.byref(ba.ws), None, N.stream_of()) != 0
 
 
+def test_fused_horizon_keeps_a_nan_env_to_itself(tmp_path):
+    """Two fused samplers of VanderPol (E = 300, n = 3, the same seeds); in one, env 5 starts from a
+    NaN state and observation. The split-f16 policy pass gives that env NaN logits and nothing
+    else: after two horizons no policy wave has timed out, and the observations and the env state
+    of every other env (its layer-3 partner env 21 included) are bit-identical in the two."""
+    pair = []
+    for sub in ("clean", "nan"):
+        args = default_msacl_args(env_name="VanderPol", env_num=300, n_step=3, seed=0, env_seed=5,
+                                  buffer_max_size=600_000, buffer_warm_size=0, save_folder=str(tmp_path / sub),
+                                  sampler_fused_horizon=True, sample_batch_size=20)
+        args = init_args(create_envs(**args), **args)
+        s, b = create_sampler(**args), create_buffer(**args)
+        s.bind_store(b)
+        assert s.fused_horizon
+        pair.append((s, b))
+    (a, _), (c, _) = pair
+    c.networks.load_state_dict(a.networks.state_dict())
+    assert torch.equal(a.obs, c.obs)
+    st, xs, steps = c.envs.get_state()
+    st[5] = float("nan")
+    c.envs.set_state(st, xs, steps)
+    c.obs[5] = float("nan")
+    for _ in range(2):
+        a.sample()
+        c.sample()
+    torch.cuda.synchronize()
+    assert _fused_errors(a) == 0 and _fused_errors(c) == 0
+    rest = torch.ones(300, dtype=torch.bool, device="cuda")
+    rest[5] = False
+    for nm, u, v in zip(("obs", "state", "xstate", "steps"), (a.obs,) + tuple(a.envs.get_state()),
+                        (c.obs,) + tuple(c.envs.get_state())):
+        if u is not None:
+            assert torch.equal(u[rest], v[rest]), (nm, int((u[rest] != v[rest]).sum()))
+
+
 def test_fused_horizon_needs_reserved_rings():
     info = N.env_info("VanderPol")
     h = ctypes.c_void_p()

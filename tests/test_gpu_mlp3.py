@@ -6,7 +6,9 @@ bound does not compound: |err| <= 2e-6 sqrt(K) sum_k |a_k w_k| + 1e-6 (tests/tes
 f32-accumulation bound), plus tanhf's ulp where the activation is tanh. Shapes: the policy
 (K1 = D, ReLU, N3 = 2A), the critics (K1 = D + A, N3 = 1), the Lyapunov network (tanh, N3 = 256),
 ragged row counts and every supported K1; the grouped (twin-critic) launch; and the MLP module's
-forward / backward through the fused launch against the per-layer launches."""
+forward / backward through the fused launch against the per-layer launches. The split-f16 layers
+(layer 2, a wide layer 3) are also held to the tighter bound their scheme implies
+(tests/split_f16_ref.py) on rows of mixed magnitude within a tile and across the weight range."""
 import ctypes
 
 import numpy as np
@@ -16,6 +18,7 @@ import torch.nn as nn
 
 import msacl_amd  # noqa: F401
 import msacl_amd._native as N
+import split_f16_ref as R
 from msacl_amd.apprfunc import _fused as F
 
 pytestmark = pytest.mark.gpu
@@ -122,20 +125,25 @@ def _kink_margin_rows(x, mods, margin=1e-5):
         z = a @ D(lin.weight).T + D(lin.bias)
         keep &= (z.abs() > margin * float(z.abs().max())).all(1)
         a = z.clamp_min(0.0)
-    return keep.to(x.device)
+    return keep.to(x.device), int((~keep).sum())
 
 
 @pytest.mark.parametrize("acts", [(nn.ReLU, nn.ReLU, nn.Identity), (nn.Tanh, nn.Tanh, nn.Identity)])
 def test_mlp_module_fused_forward_backward_matches_per_layer(acts):
     """The MLP module (apprfunc/_fused.py) through MLP3 vs through the per-layer LinearAct launches:
     outputs within the f32 summation-order bound, every gradient rtol 1e-4 / atol 1e-5 of its scale
-    (ReLU: on rows clear of the kink, _kink_margin_rows)."""
+    (ReLU: on rows clear of the kink, _kink_margin_rows; the rows dropped are counted and limited to
+    4 %: 2 x 256 units each within 1e-5 of a Gaussian-ish pre-activation's scale exclude 2.2 - 2.8 %
+    of randn rows, binomial spread 0.2 %)."""
     torch.manual_seed(0)
     mods = [nn.Linear(12, 256), acts[0](), nn.Linear(256, 256), acts[1](), nn.Linear(256, 8), acts[2]()]
     net = F.MLP(*mods).cuda()
     x = torch.randn(256 * 21, 12, device="cuda")
     if acts[0] is nn.ReLU:
-        x = x[_kink_margin_rows(x, mods)]
+        keep, dropped = _kink_margin_rows(x, mods)
+        print(f"kink margin: {dropped} of {x.shape[0]} rows excluded ({100.0 * dropped / x.shape[0]:.2f} %)")
+        assert dropped <= 0.04 * x.shape[0], dropped
+        x = x[keep]
     x = x[:256 * 20].reshape(256, 20, 12).requires_grad_(True)
     g = torch.randn(256, 20, 8, device="cuda")
     outs = []
@@ -371,11 +379,19 @@ def test_lyapunov_square_sum_fused_equals_separate(M):
         torch.testing.assert_close(a, b, rtol=0, atol=0)
 
 
+def _layer64(inp, W, b, act):
+    with np.errstate(invalid="ignore", over="ignore"):
+        return ACT[act](inp.double().cpu().numpy() @ W.double().cpu().numpy().T + b.double().cpu().numpy())
+
+
 def test_mlp3_forward_weights_past_the_split_range_and_nonfinite_rows():
     """The split-f16 hidden layers (csrc/mlp_fused.hip layer_cols_run_x3) scale weights by 2^10
     before the f16 split: a weight of 64 or more overflows its f16 hi. Such a row tile is recomputed
     by the f32 layer (x3_redo_nonfinite), so the results stay within the f32 bound. A non-finite
-    input row gives non-finite outputs in that row only; the other row tiles keep their bits."""
+    input row (a NaN, +Inf, -Inf) or one that overflows the tile's scaled f16 range (3e38) gives, in
+    each layer on the kernel's own input, a non-finite value wherever the float64 layer has one; the
+    15 other rows of its tile stay within the f32 bound of float64, and the other row tiles keep
+    their bits."""
     for K1, N3, acts in ((12, 256, (2, 2, 0)), (16, 1, (1, 1, 0))):
         ps = _params(K1, N3, seed=7)
         W1, b1, W2, b2, W3, b3 = ps
@@ -388,13 +404,25 @@ def test_mlp3_forward_weights_past_the_split_range_and_nonfinite_rows():
         y, h1, h2 = _run(x, ps, acts)
         _check_layer(h2, h1, W2, b2, acts[1], "layer 2")
         _check_layer(y, h2, W3, b3, acts[2], "layer 3")
-        xb = x.clone()
-        xb[40, 0] = float("nan")
-        yb, _, _ = _run(xb, ps, acts)
-        assert torch.all(torch.isnan(yb[40]))
-        tile = torch.arange(M, device="cuda") // 16 == 40 // 16
-        assert torch.equal(yb[~tile], y[~tile])
-        assert torch.all(torch.isfinite(yb[tile & (torch.arange(M, device="cuda") != 40)]))
+        rows = torch.arange(M, device="cuda")
+        tile = rows // 16 == 40 // 16
+        mates = tile & (rows != 40)
+        for bad in (float("nan"), float("inf"), float("-inf"), 3e38):
+            xb = x.clone()
+            xb[40, 0] = bad
+            yb, h1b, h2b = _run(xb, ps, acts)
+            if bad != bad:
+                assert torch.all(torch.isnan(yb[40]))
+            for got, ref in ((yb, y), (h1b, h1), (h2b, h2)):
+                assert torch.equal(got[~tile], ref[~tile]), bad
+            for out, inp, W, b, act, what in ((h1b, xb, W1, b1, acts[0], "layer 1"), (h2b, h1b, W2, b2, acts[1], "layer 2"),
+                                              (yb, h2b, W3, b3, acts[2], "layer 3")):
+                ref_bad = _layer64(inp[40:41], W, b, act)[0]
+                got_bad = out[40].double().cpu().numpy()
+                loud = ~np.isfinite(ref_bad)
+                assert not np.isfinite(got_bad[loud]).any(), (bad, what, int(np.isfinite(got_bad[loud]).sum()))
+                assert torch.all(torch.isfinite(out[mates])), (bad, what)
+                _check_layer(out[mates], inp[mates], W, b, act, f"{what}, tile mates of a {bad} row")
 
 
 @pytest.mark.parametrize("name,M,K1,N3,acts", CASES[:3], ids=[c[0] for c in CASES[:3]])
@@ -413,3 +441,155 @@ def test_mlp3_hidden_layer_error_near_f32_rounding(name, M, K1, N3, acts):
     ratio = np.abs(h2.double().cpu().numpy() - ref) / (2.0 ** -24 * 16 * mag + 1e-30)
     print(f"{name}: layer-2 error / (2^-24 sqrt(K) mag): max {ratio.max():.3f} mean {ratio.mean():.4f}")
     assert ratio.max() < 4.0
+
+
+# ---- the split-f16 layers against float64 with the bound of tests/split_f16_ref.py
+
+def _pad_rows(ps, acts):
+    """What the rows past M of a ragged tile hold (x = 0): h1 = act1(b1), h2 = act2(W2 h1 + b2)."""
+    W1, b1, W2, b2, W3, b3 = [t.double().cpu().numpy() for t in ps]
+    p1 = ACT[acts[0]](b1)
+    p2 = ACT[acts[1]](W2 @ p1 + b2)
+    return p1, p2
+
+
+def _split_layer_ratios(out, inp, W, b, act, pad):
+    """Per element, the split layer's |out - float64| over its tolerance on the kernel's own input:
+    split_f16_bound per 16-row tile (tmax over the tile's rows and, in a ragged tile, the padded
+    rows' input `pad`), plus what lies outside the product sum: one f32 rounding of (sum + bias),
+    2^-24 (|z| + bound), and tanhf's 2e-7 |ref| where the activation is tanh (_check_layer's term).
+    Also returns the bound itself (for the mask-flip count) and float64's pre-activation."""
+    a, w, bb = inp.double().cpu().numpy(), W.double().cpu().numpy(), b.double().cpu().numpy()
+    M = a.shape[0]
+    z = a @ w.T + bb
+    ref = ACT[act](z)
+    bound = np.empty_like(z)
+    for r0 in range(0, M, 16):
+        t = a[r0:r0 + 16]
+        tmax = float(np.abs(t).max())
+        if t.shape[0] < 16:
+            tmax = max(tmax, float(np.abs(pad).max()))
+        bound[r0:r0 + 16] = R.split_f16_bound(t, w, tmax=tmax)
+    tol = bound + 2.0 ** -24 * (np.abs(z) + bound) + (2e-7 * np.abs(ref) if act == 2 else 0.0)
+    return np.abs(out.double().cpu().numpy() - ref) / tol, tol, z
+
+
+def _check_split_layer(out, inp, W, b, act, pad, what):
+    ratio, _, _ = _split_layer_ratios(out, inp, W, b, act, pad)
+    i = np.unravel_index(np.argmax(ratio), ratio.shape)
+    print(f"{what}: worst err / bound {ratio.max():.3f} at row {i[0]} col {i[1]}")
+    assert ratio.max() <= 1.0, f"{what}: worst err / bound {ratio.max():.3f} at {i}"
+    return float(ratio.max())
+
+
+def _homogeneous_ratio(out, inp, W, b, act):
+    """test_mlp3_hidden_layer_error_near_f32_rounding's figure: |err| / (2^-24 sqrt(256) mag)."""
+    a, w, bb = inp.double().cpu().numpy(), W.double().cpu().numpy(), b.double().cpu().numpy()
+    ref = ACT[act](a @ w.T + bb)
+    mag = np.abs(a) @ np.abs(w).T + np.abs(bb)
+    return float((np.abs(out.double().cpu().numpy() - ref) / (2.0 ** -24 * 16 * mag + 1e-30)).max())
+
+
+def _check_all_layers(x, ps, acts, outs, what):
+    """Layer 1 and a narrow layer 3 (f32 MFMA) to _check_layer's bound, the split layers (layer 2,
+    layer 3 when N3 > 16) to the split bound; each on the kernel's own input."""
+    W1, b1, W2, b2, W3, b3 = ps
+    y, h1, h2 = outs
+    p1, p2 = _pad_rows(ps, acts)
+    _check_layer(h1, x, W1, b1, acts[0], f"{what} layer 1")
+    worst = [_check_split_layer(h2, h1, W2, b2, acts[1], p1, f"{what} layer 2")]
+    if W3.shape[0] > 16:
+        worst.append(_check_split_layer(y, h2, W3, b3, acts[2], p2, f"{what} layer 3"))
+    else:
+        _check_layer(y, h2, W3, b3, acts[2], f"{what} layer 3")
+    return worst
+
+
+MIXED_NETS = [("lyapunov", 12, 256, (2, 2, 0)), ("policy", 12, 8, (1, 1, 0)), ("critic", 16, 1, (1, 1, 0))]
+
+
+@pytest.mark.parametrize("M", [80, 70])
+@pytest.mark.parametrize("name,K1,N3,acts", MIXED_NETS, ids=[c[0] for c in MIXED_NETS])
+def test_mlp3_split_layers_rows_of_mixed_magnitude(name, K1, N3, acts, M):
+    """One scale per 16-row tile: rows far below their tile's maximum keep their lo halves (and,
+    from 2^-17 on, their hi halves) only as f16 subnormals. b1 = 0, so a row of h1 scales with its
+    row of x: tile 1 row 0 x 2^-14, tile 2 row 7 x 2^-20, tile 3 row 15 x 2^-8 and row 3 x 2^-17,
+    tile 4 (ragged at M = 70) every row x 2^-12, which is its own scale and must meet the
+    homogeneous ratio < 4 bar. Every element of the split layers within the split bound; the f32
+    layers within theirs; every row-tile mode the default's bits.
+    Measured worst err / tolerance (MI355X): tanh 0.12 - 0.41; ReLU layer 2 0.84 - 0.95, at elements
+    whose bias dominates the sum, where the f32 rounding of (sum + bias) is nearly the whole
+    tolerance; tile 4 at 0.056 - 0.111 of the ratio bar."""
+    ps = _params(K1, N3, seed=M + K1 + N3)
+    ps[1].zero_()
+    x = torch.rand(M, K1, generator=torch.Generator().manual_seed(2)) * 4 - 2
+    x[16 + 0] *= 2.0 ** -14
+    x[32 + 7] *= 2.0 ** -20
+    x[48 + 15] *= 2.0 ** -8
+    x[48 + 3] *= 2.0 ** -17
+    x[64:] *= 2.0 ** -12
+    x = x.cuda()
+    outs = _run(x, ps, acts)
+    y, h1, h2 = outs
+    _check_all_layers(x, ps, acts, outs, name)
+    r2 = _homogeneous_ratio(h2[64:], h1[64:], ps[2], ps[3], acts[1])
+    print(f"{name} M={M}: tile 4 layer-2 error / (2^-24 sqrt(K) mag) {r2:.3f}")
+    assert r2 < 4.0
+    for mode in (-1, 1, 3, 4):
+        N.check(N.lib().mh_mlp3_set_row_tiles(mode), "mh_mlp3_set_row_tiles")
+        try:
+            got = _run(x, ps, acts)
+        finally:
+            N.lib().mh_mlp3_set_row_tiles(0)
+        for u, v in zip(got, outs):
+            assert torch.equal(u, v), mode
+
+
+@pytest.mark.parametrize("plant", ["in_range", "redo"])
+@pytest.mark.parametrize("shift", [8, 13, 18])
+def test_mlp3_split_layers_weight_range(shift, plant):
+    """The fixed weight scale 2^10: W2 and W3 scaled by 2^-8, 2^-13, 2^-18 (lo halves, then hi
+    halves, subnormal), with single entries planted at 63.96875 (the largest weight whose scaled
+    hi is finite), 2^-24, 2^-30, 0.0 and -0.0; `redo`: also 63.99, whose hi rounds to Inf, so those
+    columns come back through x3_redo_nonfinite. Every element within the split bound.
+    Measured worst err / tolerance (MI355X): layer 2 0.21 - 0.33, layer 3 0.59 - 0.80 (bias-dominated
+    elements); the redo columns 0.59 at 2^-8, where rerunning the f32 MFMA layer gave 1.28: the redo
+    now sums exact products in double."""
+    K1, N3, acts, M = 12, 256, (2, 2, 0), 40
+    ps = _params(K1, N3, seed=shift)
+    for W in (ps[2], ps[4]):
+        W.mul_(2.0 ** -shift)
+        W[3, 5] = 63.96875
+        W[70, 130] = -63.96875
+        W[140, 7] = 2.0 ** -24
+        W[200, 255] = -2.0 ** -30
+        W[250, 0] = 0.0
+        W[255, 31] = -0.0
+        if plant == "redo":
+            W[100, 64] = 63.99
+    x = (torch.rand(M, K1, generator=torch.Generator().manual_seed(4)) * 4 - 2).cuda()
+    outs = _run(x, ps, acts)
+    assert all(torch.isfinite(t).all() for t in outs)
+    _check_all_layers(x, ps, acts, outs, f"W 2^-{shift} {plant}")
+
+
+def test_mlp3_relu_masks_flip_only_inside_the_bound():
+    """The ReLU critic at 5,120 rows: a hidden unit whose mask (h > 0) differs from the float64
+    layer's (on the kernel's own input) must have |z64| within that element's bound (layer 1:
+    _check_layer's, layer 2: the split bound): the kernel may take the other side of the kink
+    only where rounding can put it there. The count is printed (MI355X: 0 of 1,310,720 units in
+    layer 1, 1 in layer 2)."""
+    M, K1, N3, acts = 5120, 16, 1, (1, 1, 0)
+    ps = _params(K1, N3, seed=M + K1)
+    W1, b1, W2, b2, W3, b3 = ps
+    x = (torch.rand(M, K1, generator=torch.Generator().manual_seed(1)) * 4 - 2).cuda()
+    y, h1, h2 = _run(x, ps, acts)
+    D = lambda t: t.double().cpu().numpy()  # noqa: E731
+    z1 = D(x) @ D(W1).T + D(b1)
+    tol1 = 2e-6 * K1 ** 0.5 * (np.abs(D(x)) @ np.abs(D(W1)).T + np.abs(D(b1))) + 1e-6
+    flip1 = (D(h1) > 0) != (z1 > 0)
+    _, tol2, z2 = _split_layer_ratios(h2, h1, W2, b2, 1, _pad_rows(ps, acts)[0])
+    flip2 = (D(h2) > 0) != (z2 > 0)
+    print(f"mask flips of {M * 256} units: layer 1 {int(flip1.sum())}, layer 2 {int(flip2.sum())}")
+    assert np.all(np.abs(z1[flip1]) <= tol1[flip1])
+    assert np.all(np.abs(z2[flip2]) <= tol2[flip2])

@@ -81,6 +81,82 @@ def test_fused_policy_forward_scaled_operands(obs_scale, w1_scale, w2_scale):
     assert (err <= 2e-6 * mag + 1e-30).all(), (err / mag).max().item()
 
 
+def _policy64(net, obs):
+    """float64 logits of the ReLU policy and test_fused_policy_forward_scaled_operands' magnitude
+    network sum |W3| (sum |W2| |H1| + |b2|) + |b3|, per logit."""
+    with torch.no_grad():
+        W1, b1, W2, b2, W3, b3 = [t.detach().double() for t in (net[0].weight, net[0].bias, net[2].weight, net[2].bias,
+                                                                net[4].weight, net[4].bias)]
+        h1 = torch.relu(obs.double() @ W1.T + b1)
+        h2 = torch.relu(h1 @ W2.T + b2)
+        exact = h2 @ W3.T + b3
+        mag = (h1 @ W2.abs().T + b2.abs()) @ W3.abs().T + b3.abs()
+    return exact, mag
+
+
+@pytest.mark.parametrize("odd", ["zeros", "x1e4"])
+@pytest.mark.parametrize("E", [77, 160])
+def test_split_policy_forward_envs_are_isolated(E, odd):
+    """The split-f16 policy forward scales every env by its own powers of two: row i of obs scaled
+    by 10^((i mod 8) - 3), then the odd rows replaced (zeros, or x 1e4) with the even rows kept.
+    The even rows' logits are bit-identical in the two runs, and every row of both meets the
+    magnitude-network bound against float64."""
+    D, A = 12, 4
+    net = _mlp(D, A, seed=11)
+    g = torch.Generator(device="cuda").manual_seed(E)
+    obs = torch.randn(E, D, device="cuda", generator=g)
+    obs = (obs * (10.0 ** ((torch.arange(E, device="cuda") % 8) - 3.0))[:, None]).contiguous()
+    obs2 = obs.clone()
+    obs2[1::2] = 0.0 if odd == "zeros" else obs[1::2] * 1e4
+    got, got2 = _fused(net, obs, D, 2 * A), _fused(net, obs2, D, 2 * A)
+    assert torch.equal(got[0::2], got2[0::2])
+    for o, y in ((obs, got), (obs2, got2)):
+        exact, mag = _policy64(net, o)
+        err = (y.double() - exact).abs()
+        assert torch.isfinite(y).all()
+        assert (err <= 2e-6 * mag + 1e-30).all(), (err / mag).max().item()
+
+
+BAD_OBS = [float("nan"), float("inf"), float("-inf"), 3e38, 1e20, 1e12]
+
+
+@pytest.mark.parametrize("bad", BAD_OBS, ids=[str(b) for b in BAD_OBS])
+@pytest.mark.parametrize("E", [77, 160])
+def test_split_policy_forward_is_loud_or_right(E, bad):
+    """An env whose observation is non-finite or huge: env 5 gets `bad` in one column (the upper
+    half-lane's), env 67 in every column; their layer-3 partners (21, 83: pm_l3_row_half) and every
+    other env keep, bit for bit, the logits of the run where the two rows are zeros. A planted
+    row is either all finite and within the bound of its float64 value, or has no finite element;
+    it has none where the float32 torch module has a non-finite logit; 1e12 is inside the
+    documented range (csrc/policy_mlp.hip: bounds below 2^54) and must be finite and right."""
+    D, A = 12, 4
+    net = _mlp(D, A, seed=13)
+    g = torch.Generator(device="cuda").manual_seed(E + 1)
+    obs = torch.randn(E, D, device="cuda", generator=g).contiguous()
+    planted = [5, 67]
+    clean = obs.clone()
+    clean[planted] = 0.0
+    obs[5, 9] = bad
+    obs[67] = bad
+    got, ref = _fused(net, obs, D, 2 * A), _fused(net, clean, D, 2 * A)
+    others = torch.ones(E, dtype=torch.bool, device="cuda")
+    others[planted] = False
+    assert torch.equal(got[others], ref[others])
+    with torch.no_grad():
+        t32 = net(obs)
+    exact, mag = _policy64(net, obs)
+    for i in planted:
+        fin = torch.isfinite(got[i])
+        assert fin.all() or not fin.any(), (i, got[i].tolist())
+        if not torch.isfinite(t32[i]).all():
+            assert not fin.any(), (i, got[i].tolist(), t32[i].tolist())
+        if bad == 1e12:
+            assert fin.all(), (i, got[i].tolist())
+        if fin.all():
+            err = (got[i].double() - exact[i]).abs()
+            assert (err <= 2e-6 * mag[i] + 1e-30).all(), (i, (err / mag[i]).max().item())
+
+
 def test_fused_policy_rejects_unsupported_shapes():
     n = ctypes.c_int64()
     assert N.lib().mh_policy_packed_size(17, ctypes.byref(n)) == -1
