@@ -791,6 +791,79 @@ int mh_audit_step(mh_env_t h, const float* logits, const float* act_in, float* o
 int mh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c, const float* w, const float* s,
                         float alpha1, float alpha2, const mh_certificate_out_t* out, float* resid, void* stream);
 
+/* ---- robustness sweep: the audited closed loop under sensor and actuator noise (new: the
+ * reference's README shows tracking "with noises" but ships no code for it) ----
+ * The audit above with a per-env disturbance around the unchanged env step, so that L noise
+ * levels x M paired trajectories are ONE lockstep batch of L * M envs (csrc/robustness.h):
+ *   sensor    the policy sees obs_meas[i] = obs[i] + (obs_sigma[e] * obs_weight[i]) * xi_i; the
+ *             true observation is still what is stepped, scored (q, cost, termination) and stored
+ *   actuator  with u_nom the clipped mode of the logits (or act_in as given) and
+ *             half_i = (hi_i - lo_i) / 2, the applied action is
+ *             u_i = clip(u_nom_i + half_i * (act_bias[e][i] + act_sigma[e] * zeta_i), lo_i, hi_i);
+ *             traj_act stores the applied action
+ * All float32, the operations separate and in the order written. xi and zeta are standard normals
+ * of the engine's Philox4x32-10 keyed by seed with counter (noise_id[e], stream, tick), float32
+ * Box-Muller, four per draw: stream 16 + i / 4 for xi_i, 24 + i / 4 for zeta_i (no other draw of
+ * the engine uses these ids); tick 0 in mh_robust_begin, t for step t's action, t + 1 for the
+ * observation step t produces. An env whose obs_sigma (act_sigma) is 0 skips the draw: its
+ * obs_meas row is the true row bit for bit. With act_sigma and act_bias both NULL the nominal
+ * action is applied as it is, so a NULL or all-NULL disturbance is mh_audit_step bit for bit.
+ * Equal noise_id (with equal seed) means equal realisations: levels that share ids are paired
+ * (common random numbers). Negative sigmas are undefined. Every array is [E]-indexed like the
+ * trajectory; every pointer may be NULL for its default. */
+typedef struct {
+  const float* obs_sigma;   /* [E], NULL: 0 */
+  const float* obs_weight;  /* [obs_dim], NULL: 1 */
+  const float* act_sigma;   /* [E], NULL: 0 */
+  const float* act_bias;    /* [E][act_dim], NULL: 0 */
+  const int32_t* noise_id;  /* [E], NULL: e */
+  uint64_t seed;
+} mh_disturbance_t;
+
+/* Per-env results of mh_robust_scan, each [E] and required. Over the trajectory's rows t = 0..len:
+ *   q_peak / t_peak     max of q_t / its first argmax
+ *   tail_max / tail_mean / tail_count
+ *                       over the last rows max(0, len - tail_window + 1)..len: the max of q_t, its
+ *                       mean (float64 sum / count) and the number of rows
+ *   settle              0 if no q_t > settle_frac * q_0, else 1 + the last such t; len + 1 means
+ *                       "not settled"
+ *   pairs_out / viol_out / worst_out
+ *                       the practical decay: mh_certificate_scan's pairs (t, k), k = 1..n,
+ *                       t + k <= len, restricted to starts OUTSIDE the residual ball,
+ *                       q_t > ball_factor * tail_max: their count, those with
+ *                       V_{t+k} > s_{k-1} V_t, and the largest V_{t+k} - s_{k-1} V_t (-inf
+ *                       without a pair). Under noise the certificate can only be expected to
+ *                       hold outside the ball the trajectory ends up in. */
+typedef struct {
+  float* q_peak;
+  int32_t* t_peak;
+  float* tail_max;
+  double* tail_mean;
+  int32_t* tail_count;
+  int32_t* settle;
+  int32_t* pairs_out;
+  int32_t* viol_out;
+  float* worst_out;
+} mh_robust_out_t;
+
+/* mh_audit_begin, and the first policy input obs_meas [E][obs_dim] (required) from row 0 at tick
+ * 0. d NULL: no disturbance (obs_meas = obs). */
+int mh_robust_begin(mh_env_t h, const float* reset_states, float* obs, float* obs_meas,
+                    const mh_audit_traj_t* traj, const mh_disturbance_t* d, void* stream);
+/* mh_audit_step under the disturbance d (NULL: none): logits are the policy's output for the
+ * obs_meas of the previous call; obs receives the TRUE observation, obs_meas the next policy
+ * input. A frozen env's rows of obs and obs_meas are never written again. MH_EINVAL for a null
+ * required pointer, a num_envs mismatch, t outside [0, T) and rows (obs, obs_meas, traj_obs,
+ * traj_act, act_in, logits) not aligned for the vector accesses (16 B for rows of a multiple of 4
+ * floats, 8 B for even rows). */
+int mh_robust_step(mh_env_t h, const float* logits, const float* act_in, float* obs, float* obs_meas,
+                   const mh_audit_traj_t* traj, const mh_disturbance_t* d, int32_t t, void* stream);
+/* The robustness numbers of every trajectory (traj: q, v, len, num_envs, T), s the algorithm's
+ * start_lya_coef [n]. MH_EINVAL unless 1 <= n <= 64, 1 <= tail_window <= T + 1, 0 <= T <= max_step
+ * and settle_frac, ball_factor finite and >= 0. Rows beyond an env's len are never read. */
+int mh_robust_scan(const mh_audit_traj_t* traj, int32_t n, const float* s, int32_t tail_window,
+                   float settle_frac, float ball_factor, const mh_robust_out_t* out, void* stream);
+
 /* ---- prioritized replay (new: the reference trainer expects buffer.update_batch(idx, prio),
  * RL/trainer/nstep_off_serial_trainer.py:93-95, but ships no prioritized buffer) ---- */
 /* sum-tree over `capacity` leaves (tree: float64 [2*pow2]); leaf i priority p_i. */

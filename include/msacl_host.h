@@ -52,6 +52,16 @@ int mhh_audit_step(mhh_env_t h, const float* logits, const float* act_in, float*
 int mhh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c, const float* w, const float* s,
                          float alpha1, float alpha2, const mh_certificate_out_t* out, float* resid);
 
+/* The robustness sweep, the host twins of mh_robust_begin / mh_robust_step / mh_robust_scan
+ * (msacl_hip.h: same arguments minus the stream, the same per-env code, csrc/robustness.h, and
+ * the same rejections, the row alignment included). */
+int mhh_robust_begin(mhh_env_t h, const float* reset_states, float* obs, float* obs_meas,
+                     const mh_audit_traj_t* traj, const mh_disturbance_t* d);
+int mhh_robust_step(mhh_env_t h, const float* logits, const float* act_in, float* obs, float* obs_meas,
+                    const mh_audit_traj_t* traj, const mh_disturbance_t* d, int32_t t);
+int mhh_robust_scan(const mh_audit_traj_t* traj, int32_t n, const float* s, int32_t tail_window, float settle_frac,
+                    float ball_factor, const mh_robust_out_t* out);
+
 /* MSACL target / certificate math (RL/algorithm/msacl.py), the host twins of mh_msacl_* in
  * msacl_hip.h (same arguments minus the stream): */
 int mhh_msacl_q_target(const float* q1, const float* q2, const float* q1t, const float* q2t, const float* next_logp,

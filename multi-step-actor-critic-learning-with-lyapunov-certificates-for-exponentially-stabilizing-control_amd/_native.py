@@ -86,11 +86,26 @@ class CertificateOut(ctypes.Structure):
                                     "hi_excess", "lya_worst", "resid_sum")]
 
 
+class Disturbance(ctypes.Structure):
+    """mh_disturbance_t (include/msacl_hip.h)."""
+    _fields_ = [("obs_sigma", c_vp), ("obs_weight", c_vp), ("act_sigma", c_vp), ("act_bias", c_vp),
+                ("noise_id", c_vp), ("seed", c_u64)]
+
+
+class RobustOut(ctypes.Structure):
+    """mh_robust_out_t (include/msacl_hip.h)."""
+    _fields_ = [(k, c_vp) for k in ("q_peak", "t_peak", "tail_max", "tail_mean", "tail_count", "settle", "pairs_out",
+                                    "viol_out", "worst_out")]
+
+
 _AUDIT_PROTOS = {  # entry points shared by both libraries (the device ones take a trailing stream)
     "audit_begin": [c_vp, c_vp, c_vp, ctypes.POINTER(AuditTraj)],
     "audit_step": [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(AuditTraj), c_i32],
     "certificate_scan": [ctypes.POINTER(AuditTraj), c_i32, c_vp, c_vp, c_vp, c_f32, c_f32,
                          ctypes.POINTER(CertificateOut), c_vp],
+    "robust_begin": [c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(AuditTraj), ctypes.POINTER(Disturbance)],
+    "robust_step": [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.POINTER(AuditTraj), ctypes.POINTER(Disturbance), c_i32],
+    "robust_scan": [ctypes.POINTER(AuditTraj), c_i32, c_vp, c_i32, c_f32, c_f32, ctypes.POINTER(RobustOut)],
 }
 
 # name -> (restype, argtypes)

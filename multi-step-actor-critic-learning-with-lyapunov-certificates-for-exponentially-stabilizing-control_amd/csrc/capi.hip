@@ -689,6 +689,115 @@ int mh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c, 
   return MH_OK;
 }
 
+// ------------------------------------------------------------------ robustness sweep
+static mh::Disturb disturb_of(const mh_disturbance_t* d) {
+  mh::Disturb o;
+  std::memset(&o, 0, sizeof(o));
+  if (d) {
+    o.obs_sigma = d->obs_sigma;
+    o.obs_weight = d->obs_weight;
+    o.act_sigma = d->act_sigma;
+    o.act_bias = d->act_bias;
+    o.noise_id = d->noise_id;
+    o.seed = d->seed;
+  }
+  return o;
+}
+
+static int robust_rows(mh_env_t h, const mh::RobustArgs& r, const char* who) {
+  const int D = h->info.obs_dim, A = h->info.act_dim;
+  if (!mh::robust_row_aligned(r.a.obs, D) || !mh::robust_row_aligned(r.obs_meas, D) ||
+      !mh::robust_row_aligned(r.a.traj_obs, D) || !mh::robust_row_aligned(r.a.traj_act, A) ||
+      !mh::robust_row_aligned(r.a.act_in, A) || !mh::robust_row_aligned(r.a.logits, 2 * A))
+    return fail(MH_EINVAL, std::string(who) + ": misaligned rows");
+  return MH_OK;
+}
+
+int mh_robust_begin(mh_env_t h, const float* reset_states, float* obs, float* obs_meas,
+                    const mh_audit_traj_t* traj, const mh_disturbance_t* d, void* stream) {
+  mh::RobustArgs r;
+  std::memset(&r, 0, sizeof(r));
+  if (int rc = audit_args(h, traj, "mh_robust_begin", &r.a)) return rc;
+  if (!obs || !obs_meas) return fail(MH_EINVAL, "mh_robust_begin: null obs or obs_meas");
+  r.a.obs = obs;
+  r.a.q_row = traj->q;
+  r.a.traj_obs = traj->traj_obs;
+  r.obs_meas = obs_meas;
+  r.d = disturb_of(d);
+  r.t = 0;
+  if (int rc = robust_rows(h, r, "mh_robust_begin")) return rc;
+  if (int rc = mh_env_reset(h, reset_states, obs, stream)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  MH_HIP(hipMemsetAsync(traj->q, 0, sizeof(float) * ((size_t)traj->T + 1) * h->E, st));
+  MH_HIP(mh::launch_robust_begin(h->env_id, r, st));
+  return MH_OK;
+}
+
+int mh_robust_step(mh_env_t h, const float* logits, const float* act_in, float* obs, float* obs_meas,
+                   const mh_audit_traj_t* traj, const mh_disturbance_t* d, int32_t t, void* stream) {
+  mh::RobustArgs r;
+  std::memset(&r, 0, sizeof(r));
+  if (int rc = audit_args(h, traj, "mh_robust_step", &r.a)) return rc;
+  if (!obs || !obs_meas) return fail(MH_EINVAL, "mh_robust_step: null obs or obs_meas");
+  if (!logits && !act_in) return fail(MH_EINVAL, "mh_robust_step: need logits or act_in");
+  if (t < 0 || t >= traj->T) return fail(MH_EINVAL, "mh_robust_step: t outside [0, T)");
+  const int64_t E = h->E;
+  r.a.obs = obs;
+  r.a.logits = act_in ? nullptr : logits;
+  r.a.act_in = act_in;
+  r.a.q_row = traj->q + ((int64_t)t + 1) * E;
+  r.a.traj_obs = traj->traj_obs ? traj->traj_obs + ((int64_t)t + 1) * E * h->info.obs_dim : nullptr;
+  r.a.traj_act = traj->traj_act ? traj->traj_act + (int64_t)t * E * h->info.act_dim : nullptr;
+  r.obs_meas = obs_meas;
+  r.d = disturb_of(d);
+  r.t = t;
+  if (int rc = robust_rows(h, r, "mh_robust_step")) return rc;
+  if (int rc = flush_pending(h, stream)) return rc;
+  MH_HIP(mh::launch_robust_step(h->env_id, r, (hipStream_t)stream));
+  return MH_OK;
+}
+
+int mh_robust_scan(const mh_audit_traj_t* traj, int32_t n, const float* s, int32_t tail_window,
+                   float settle_frac, float ball_factor, const mh_robust_out_t* out, void* stream) {
+  if (!traj || !out || !s) return fail(MH_EINVAL, "mh_robust_scan: null argument");
+  if (n < 1 || n > mh::CERT_MAX_N) return fail(MH_EINVAL, "mh_robust_scan: n outside [1, 64]");
+  if (traj->T < 0 || traj->T > mh::MAX_STEP) return fail(MH_EINVAL, "mh_robust_scan: T outside [0, max_step]");
+  if (tail_window < 1 || tail_window > traj->T + 1)
+    return fail(MH_EINVAL, "mh_robust_scan: tail_window outside [1, T + 1]");
+  if (!(settle_frac >= 0.0f) || !std::isfinite(settle_frac))
+    return fail(MH_EINVAL, "mh_robust_scan: settle_frac negative or not finite");
+  if (!(ball_factor >= 0.0f) || !std::isfinite(ball_factor))
+    return fail(MH_EINVAL, "mh_robust_scan: ball_factor negative or not finite");
+  if (traj->num_envs <= 0 || !traj->q || !traj->v || !traj->len)
+    return fail(MH_EINVAL, "mh_robust_scan: incomplete trajectory (q, v, len)");
+  if (!out->q_peak || !out->t_peak || !out->tail_max || !out->tail_mean || !out->tail_count || !out->settle ||
+      !out->pairs_out || !out->viol_out || !out->worst_out)
+    return fail(MH_EINVAL, "mh_robust_scan: incomplete outputs");
+  mh::RobustScanArgs a;
+  std::memset(&a, 0, sizeof(a));
+  a.E = traj->num_envs;
+  a.v = traj->v;
+  a.q = traj->q;
+  a.len = traj->len;
+  a.T = traj->T;
+  a.n = n;
+  a.W = tail_window;
+  a.s = s;
+  a.settle_frac = settle_frac;
+  a.ball_factor = ball_factor;
+  a.q_peak = out->q_peak;
+  a.t_peak = out->t_peak;
+  a.tail_max = out->tail_max;
+  a.tail_mean = out->tail_mean;
+  a.tail_count = out->tail_count;
+  a.settle = out->settle;
+  a.pairs_out = out->pairs_out;
+  a.viol_out = out->viol_out;
+  a.worst_out = out->worst_out;
+  MH_HIP(mh::launch_robust_scan(a, (hipStream_t)stream));
+  return MH_OK;
+}
+
 static int rollout_impl(mh_env_t h, const float* logits, const float* act_in, const float* logp_in,
                         const float* reset_states, float* obs, const mh_window_store_t* store,
                         float* act_out, float* logp_out, void* stream, bool defer) {

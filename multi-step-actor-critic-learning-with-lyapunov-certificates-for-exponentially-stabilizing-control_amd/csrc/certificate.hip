@@ -14,41 +14,6 @@
 
 namespace mh {
 
-// One env's row of a row-major [E][N] float tensor as the widest aligned vector accesses (row
-// offsets are multiples of N floats; the launchers check the base alignment)
-template <int N>
-__device__ __forceinline__ void load_row(const float* p, float* out) {
-  if constexpr (N % 4 == 0) {
-#pragma unroll
-    for (int i = 0; i < N; i += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(p + i);
-      out[i] = v.x, out[i + 1] = v.y, out[i + 2] = v.z, out[i + 3] = v.w;
-    }
-  } else if constexpr (N % 2 == 0) {
-#pragma unroll
-    for (int i = 0; i < N; i += 2) {
-      const float2 v = *reinterpret_cast<const float2*>(p + i);
-      out[i] = v.x, out[i + 1] = v.y;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < N; ++i) out[i] = p[i];
-  }
-}
-template <int N>
-__device__ __forceinline__ void store_row(float* p, const float* v) {
-  if constexpr (N % 4 == 0) {
-#pragma unroll
-    for (int i = 0; i < N; i += 4) *reinterpret_cast<float4*>(p + i) = make_float4(v[i], v[i + 1], v[i + 2], v[i + 3]);
-  } else if constexpr (N % 2 == 0) {
-#pragma unroll
-    for (int i = 0; i < N; i += 2) *reinterpret_cast<float2*>(p + i) = make_float2(v[i], v[i + 1]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < N; ++i) p[i] = v[i];
-  }
-}
-
 // mh_audit_begin after the reset: row 0 of the trajectory columns and the cleared accumulators
 template <class Env>
 __global__ __launch_bounds__(BLK) void k_audit_begin(AuditArgs a) {

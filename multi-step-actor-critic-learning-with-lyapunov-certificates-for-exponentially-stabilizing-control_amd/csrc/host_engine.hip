@@ -13,11 +13,13 @@
 #include <stdint.h>
 #include <string.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
 #include "msacl_host.h"
 #include "certificate.h"
+#include "robustness.h"
 #include "reset_draw.h"
 
 #pragma clang fp contract(off)
@@ -149,6 +151,61 @@ void audit_step_all(HostEnv& h, const float* logits, const float* act_in, float*
     const int status = mh::audit_env_step<Env>(&h.state[e * S], &h.xstate[e * (XS > 0 ? XS : 1)], k, u, tab, obs2, &q, &r);
     h.steps[e] = k + 1;
     for (int i = 0; i < D; ++i) obs[e * D + i] = obs2[i];
+    tr->q[((int64_t)t + 1) * E + e] = q;
+    if (tr->traj_obs)
+      for (int i = 0; i < D; ++i) tr->traj_obs[(((int64_t)t + 1) * E + e) * D + i] = obs2[i];
+    if (tr->traj_act)
+      for (int i = 0; i < A; ++i) tr->traj_act[((int64_t)t * E + e) * A + i] = u[i];
+    tr->len[e] += 1;
+    tr->status[e] = status;
+    tr->ret[e] += (double)(r * tr->reward_scale);
+    tr->cost[e] += (double)(q * tr->cost_scale);
+  }
+}
+
+// mh_robust_begin / mh_robust_step over the batch (robustness.h: the kernels' per-env code)
+mh::Disturb disturb_of(const mh_disturbance_t* d) {
+  mh::Disturb o;
+  memset(&o, 0, sizeof(o));
+  if (d) {
+    o.obs_sigma = d->obs_sigma;
+    o.obs_weight = d->obs_weight;
+    o.act_sigma = d->act_sigma;
+    o.act_bias = d->act_bias;
+    o.noise_id = d->noise_id;
+    o.seed = d->seed;
+  }
+  return o;
+}
+
+template <class Env>
+void robust_begin_all(HostEnv& h, const float* rs_in, float* obs, float* obs_meas, const mh_audit_traj_t* tr,
+                      const mh::Disturb& d) {
+  audit_begin_all<Env>(h, rs_in, obs, tr);
+  for (int64_t e = 0; e < h.E; ++e) mh::robust_measure<Env::D>(d, e, 0, obs + e * Env::D, obs_meas + e * Env::D);
+}
+
+template <class Env>
+void robust_step_all(HostEnv& h, const float* logits, const float* act_in, float* obs, float* obs_meas,
+                     const mh_audit_traj_t* tr, const mh::Disturb& d, int t) {
+  constexpr int D = Env::D, A = Env::A, S = Env::S, XS = Env::XS;
+  const int64_t E = h.E;
+  const double* tab = h.tab.empty() ? nullptr : h.tab.data();
+  for (int64_t e = 0; e < E; ++e) {
+    if (tr->status[e] != mh::AUDIT_RUNNING) continue;  // frozen
+    float u[A];
+    if (act_in) {
+      for (int i = 0; i < A; ++i) u[i] = act_in[e * A + i];
+    } else {
+      mh::audit_mode_action<Env>(logits + e * 2 * A, u);
+    }
+    mh::robust_actuate<Env>(d, e, (uint64_t)t, u);
+    float obs2[D], q, r;
+    const int k = h.steps[e];
+    const int status = mh::audit_env_step<Env>(&h.state[e * S], &h.xstate[e * (XS > 0 ? XS : 1)], k, u, tab, obs2, &q, &r);
+    h.steps[e] = k + 1;
+    for (int i = 0; i < D; ++i) obs[e * D + i] = obs2[i];
+    mh::robust_measure<D>(d, e, (uint64_t)t + 1, obs2, obs_meas + e * D);
     tr->q[((int64_t)t + 1) * E + e] = q;
     if (tr->traj_obs)
       for (int i = 0; i < D; ++i) tr->traj_obs[(((int64_t)t + 1) * E + e) * D + i] = obs2[i];
@@ -337,6 +394,78 @@ int mhh_certificate_scan(const mh_audit_traj_t* traj, int32_t n, const float* c,
     out->hi_excess[e] = o.hi_excess;
     out->lya_worst[e] = o.lya_worst;
     out->resid_sum[e] = o.resid_sum;
+  }
+  return MH_OK;
+}
+
+// ------------------------------------------------------------------ robustness sweep (host)
+// The host loops need no alignment; the rows are checked all the same, so that a call the device
+// library rejects is rejected here too.
+static int robust_rows(HostEnv* h, const float* logits, const float* act_in, const float* obs, const float* obs_meas,
+                       const mh_audit_traj_t* tr, int64_t t, const char* who) {
+  const int D = h->D, A = h->A;
+  const float* to = tr->traj_obs ? tr->traj_obs + (t + 1) * h->E * D : nullptr;
+  const float* ta = tr->traj_act && t >= 0 ? tr->traj_act + t * h->E * A : nullptr;
+  if (!mh::robust_row_aligned(obs, D) || !mh::robust_row_aligned(obs_meas, D) || !mh::robust_row_aligned(to, D) ||
+      !mh::robust_row_aligned(ta, A) || !mh::robust_row_aligned(act_in, A) ||
+      !mh::robust_row_aligned(act_in ? nullptr : logits, 2 * A))
+    return fail(MH_EINVAL, std::string(who) + ": misaligned rows");
+  return MH_OK;
+}
+
+int mhh_robust_begin(mhh_env_t hv, const float* reset_states, float* obs, float* obs_meas,
+                     const mh_audit_traj_t* traj, const mh_disturbance_t* d) {
+  HostEnv* h = static_cast<HostEnv*>(hv);
+  if (int rc = audit_check(h, traj, "mhh_robust_begin")) return rc;
+  if (!obs || !obs_meas) return fail(MH_EINVAL, "mhh_robust_begin: null obs or obs_meas");
+  if (int rc = robust_rows(h, nullptr, nullptr, obs, obs_meas, traj, -1, "mhh_robust_begin")) return rc;
+  const mh::Disturb dd = disturb_of(d);
+  MHH_DISPATCH(h->env_id, robust_begin_all<Env>(*h, reset_states, obs, obs_meas, traj, dd));
+  return MH_OK;
+}
+
+int mhh_robust_step(mhh_env_t hv, const float* logits, const float* act_in, float* obs, float* obs_meas,
+                    const mh_audit_traj_t* traj, const mh_disturbance_t* d, int32_t t) {
+  HostEnv* h = static_cast<HostEnv*>(hv);
+  if (int rc = audit_check(h, traj, "mhh_robust_step")) return rc;
+  if (!obs || !obs_meas) return fail(MH_EINVAL, "mhh_robust_step: null obs or obs_meas");
+  if (!logits && !act_in) return fail(MH_EINVAL, "mhh_robust_step: need logits or act_in");
+  if (t < 0 || t >= traj->T) return fail(MH_EINVAL, "mhh_robust_step: t outside [0, T)");
+  if (int rc = robust_rows(h, logits, act_in, obs, obs_meas, traj, t, "mhh_robust_step")) return rc;
+  const mh::Disturb dd = disturb_of(d);
+  MHH_DISPATCH(h->env_id, robust_step_all<Env>(*h, logits, act_in, obs, obs_meas, traj, dd, t));
+  return MH_OK;
+}
+
+int mhh_robust_scan(const mh_audit_traj_t* traj, int32_t n, const float* s, int32_t tail_window, float settle_frac,
+                    float ball_factor, const mh_robust_out_t* out) {
+  if (!traj || !out || !s) return fail(MH_EINVAL, "mhh_robust_scan: null argument");
+  if (n < 1 || n > mh::CERT_MAX_N) return fail(MH_EINVAL, "mhh_robust_scan: n outside [1, 64]");
+  if (traj->T < 0 || traj->T > mh::MAX_STEP) return fail(MH_EINVAL, "mhh_robust_scan: T outside [0, max_step]");
+  if (tail_window < 1 || tail_window > traj->T + 1)
+    return fail(MH_EINVAL, "mhh_robust_scan: tail_window outside [1, T + 1]");
+  if (!(settle_frac >= 0.0f) || !std::isfinite(settle_frac))
+    return fail(MH_EINVAL, "mhh_robust_scan: settle_frac negative or not finite");
+  if (!(ball_factor >= 0.0f) || !std::isfinite(ball_factor))
+    return fail(MH_EINVAL, "mhh_robust_scan: ball_factor negative or not finite");
+  if (traj->num_envs <= 0 || !traj->q || !traj->v || !traj->len)
+    return fail(MH_EINVAL, "mhh_robust_scan: incomplete trajectory (q, v, len)");
+  if (!out->q_peak || !out->t_peak || !out->tail_max || !out->tail_mean || !out->tail_count || !out->settle ||
+      !out->pairs_out || !out->viol_out || !out->worst_out)
+    return fail(MH_EINVAL, "mhh_robust_scan: incomplete outputs");
+  for (int64_t e = 0; e < traj->num_envs; ++e) {
+    mh::RobustRow o;
+    mh::robust_scan_env(traj->v, traj->q, traj->num_envs, e, traj->len[e], traj->T, n, s, tail_window, settle_frac,
+                        ball_factor, &o);
+    out->q_peak[e] = o.q_peak;
+    out->t_peak[e] = o.t_peak;
+    out->tail_max[e] = o.tail_max;
+    out->tail_mean[e] = o.tail_mean;
+    out->tail_count[e] = o.tail_count;
+    out->settle[e] = o.settle;
+    out->pairs_out[e] = o.pairs_out;
+    out->viol_out[e] = o.viol_out;
+    out->worst_out[e] = o.worst_out;
   }
   return MH_OK;
 }

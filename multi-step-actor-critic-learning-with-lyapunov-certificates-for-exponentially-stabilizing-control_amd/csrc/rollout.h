@@ -5,6 +5,7 @@
 
 #include "env_math.h"
 #include "philox.h"
+#include "robustness.h"
 
 namespace mh {
 
@@ -179,6 +180,29 @@ struct ScanArgs {
 hipError_t launch_audit_begin(int env_id, const AuditArgs& a, hipStream_t st);  // a.obs: the reset's observations
 hipError_t launch_audit_step(int env_id, const AuditArgs& a, hipStream_t st);
 hipError_t launch_certificate_scan(const ScanArgs& a, hipStream_t st);
+
+// the robustness sweep (robustness.hip): the audit's lockstep with a per-env disturbance, and the
+// scan of the finished q / V trajectories
+struct RobustArgs {
+  AuditArgs a;      // as for the audit; a.obs stays the TRUE observation
+  float* obs_meas;  // [E][D] out: the policy's next input of every live env
+  Disturb d;
+  int32_t t;        // lockstep index (the Philox tick): action t, observation t + 1
+};
+struct RobustScanArgs {
+  int64_t E;
+  const float *v, *q;  // [T + 1][E]
+  const int32_t* len;  // [E]
+  int T, n, W;
+  const float* s;      // [n]
+  float settle_frac, ball_factor;
+  float *q_peak, *tail_max, *worst_out;
+  double* tail_mean;
+  int32_t *t_peak, *tail_count, *settle, *pairs_out, *viol_out;
+};
+hipError_t launch_robust_begin(int env_id, const RobustArgs& r, hipStream_t st);  // r.a.obs: the reset's observations
+hipError_t launch_robust_step(int env_id, const RobustArgs& r, hipStream_t st);
+hipError_t launch_robust_scan(const RobustScanArgs& a, hipStream_t st);
 
 hipError_t launch_rollout(int env_id, const StepArgs& a, hipStream_t st);
 hipError_t launch_gae(const float* val, const float* val2, const float* rew, const uint8_t* done, int64_t E,
